@@ -25,7 +25,10 @@ Multi-GPU: the image/batch axis shards with no data-path collective -- every ran
 is used for the barrier and the max-over-ranks reduction, for a self-test of the transport (one 1080p frame per rank through
 ncclSend/ncclRecv, bytes compared; after the headline and M1, which use no transport, and before every leg that does) and in the `C4_e2e` leg for the scatter of frames from rank 0 and the gather of results.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+        --dump-outputs DIR: after the headline's timed steps, rank 0 writes what the timed call returned in its last step,
+        g and h, as DIR/g.npy and DIR/h.npy (float32, the rows _dump_rows() names: 32 MiB in all) -- the inputs are seeded,
+        so that two builds can be compared output for output.
         N > 1 without WORLD_SIZE in the environment: this process starts N rank processes
         (one per GPU, RCCL rendezvous on 127.0.0.1) BEFORE touching the GPU, waits for them and
         exits with their status; rank 0 prints the JSON line.
@@ -56,6 +59,8 @@ EXIT_WATCHDOG = 3     # secondary legs ran into --extra-timeout: headline printe
 EXIT_LEGS_FAILED = 5  # a secondary leg raised: headline + the legs finished so far are printed first
 EXIT_TERMINATED = 4   # SIGTERM (another rank failed / the launcher gave up): whatever was measured is printed first
 LEAD_IN_MS = 20.0
+DUMP_ROWS = 1024      # rows of each output plane --dump-outputs writes (2 planes x 1024 x 4096 f32 = 32 MiB, under the 64 MB cap)
+DUMP_SEED = 4096      # fixed: the same rows in every run and every build
 
 
 def _dist_env():
@@ -156,6 +161,23 @@ def _time_steps(torch, fn, steps, warmup, barrier, repeats=1, idle_s=0.0):
         walls.append(t1 - t0)
         evs.append(ev0.elapsed_time(ev1))
     return walls, evs
+
+
+def _dump_rows(rows=ROWS, n=DUMP_ROWS):
+    """the rows --dump-outputs writes, ascending: the 8 at either edge (where the border handling acts) and a seeded sample of the rest"""
+    import numpy as np
+    edge = np.r_[0:8, rows - 8:rows]
+    inner = np.random.default_rng(DUMP_SEED).choice(np.arange(8, rows - 8), n - len(edge), replace=False)
+    return np.sort(np.concatenate([edge, inner]))
+
+
+def _dump_outputs(torch, d, planes):
+    """--dump-outputs: every plane of `planes` (name -> device tensor, already synchronised) as d/<name>.npy, float32, rows _dump_rows()"""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, p in planes.items():
+        idx = torch.from_numpy(_dump_rows(p.shape[0])).to(p.device)
+        np.save(os.path.join(d, name + ".npy"), p.index_select(0, idx).float().cpu().numpy())
 
 
 def _telemetry_files(torch, dev_index):
@@ -386,10 +408,14 @@ def main():
     ap.add_argument("--traffic-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--no-live-traffic", action="store_true", help="do not start the two rocprofv3 --pmc child runs; roofline.traffic is then replayed from profiles/traffic.json")
     ap.add_argument("--leg-repeats", type=int, default=7, help="repeats of every secondary leg's timed region (median reported)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the headline's timed steps, write the g and h its last step returned as DIR/g.npy, DIR/h.npy (float32, a fixed sample of rows)")
     args = ap.parse_args()
     LEAD_IN_MS = max(0.0, args.lead_ms)
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
     if args.traffic_child:
         return _traffic_child()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -562,6 +588,9 @@ def main():
     settle(step, f)
     R = max(1, args.repeats)
     walls, evs = _time_steps(torch, step, args.steps, args.warmup, barrier, repeats=R)
+    if args.dump_outputs and rank == 0:   # before any other leg writes g / h
+        _dump_outputs(torch, args.dump_outputs, {"g": g, "h": h})
+        out["dump_outputs"] = os.path.abspath(args.dump_outputs)
     # per repeat: the slowest rank; then the median over the repeats
     both = max_over_ranks(*(walls + evs))
     walls, evs = list(both[:R]), list(both[R:])

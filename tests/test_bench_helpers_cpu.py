@@ -46,3 +46,24 @@ def test_bytes_per_pixel_table_matches_the_survey(bench):
     b = bench.BYTES_PER_PIX
     assert (b["M1"], b["M2"], b["M4"], b["M5"], b["M6"], b["M6s"]) == (32, 40, 52, 84, 48, 56)
     assert b["M2_u8"] == 37 and b["C4_u8_feat3"] == 13
+
+
+def test_dump_rows_are_fixed_distinct_and_hold_the_edges(bench):
+    """--dump-outputs writes the same rows in every run: both 8-row edges and a seeded sample of the rest, within the 64 MB cap"""
+    import numpy as np
+    r = bench._dump_rows()
+    assert np.array_equal(r, bench._dump_rows())
+    assert len(r) == bench.DUMP_ROWS and np.all(np.diff(r) > 0) and 0 <= r[0] and r[-1] < bench.ROWS
+    assert set(range(8)) | set(range(bench.ROWS - 8, bench.ROWS)) <= set(r.tolist())
+    assert 2 * len(r) * bench.COLS * 4 <= 64e6     # g and h, float32
+
+
+def test_dump_outputs_writes_the_named_rows_as_float32(bench, tmp_path):
+    import numpy as np
+    import torch
+    plane = torch.arange(bench.ROWS, dtype=torch.float32)[:, None].expand(bench.ROWS, bench.COLS)   # every pixel holds its row index
+    bench._dump_outputs(torch, str(tmp_path / "d"), {"g": plane, "h": -plane})
+    g, h = np.load(tmp_path / "d" / "g.npy"), np.load(tmp_path / "d" / "h.npy")
+    assert g.dtype == h.dtype == np.float32 and g.shape == h.shape == (bench.DUMP_ROWS, bench.COLS)
+    assert np.array_equal(g[:, 0], bench._dump_rows().astype(np.float32)) and np.array_equal(h, -g)
+    assert (g == g[:, :1]).all()

@@ -526,6 +526,34 @@ def test_bench_starts_its_own_ranks_and_watchdog_emits_the_headline(tmp_path):
     assert d["n_gpus"] == 1 and d["value"] > 0 and "watchdog" in d["extra_error"]
 
 
+def test_bench_dump_outputs_are_what_the_timed_call_returns(tmp_path):
+    """bench.py --dump-outputs DIR: DIR/g.npy and DIR/h.npy are the rows bench._dump_rows() names of the g / h the headline call
+    (setup_steer of the seeded 4096^2 image at theta 0.3) returns, bit for bit; the line carries --steps and ms_per_step."""
+    import importlib.util
+    import subprocess
+    import sys
+    import torch
+    import cvsteer_amd as cv
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    d = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "2", "--repeats", "2", "--no-extra", "--no-cpu",
+                        "--no-live-traffic", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = _json_line(r.stdout)
+    assert line["steps"] == 4 and line["ms_per_step"] > 0 and line["dump_outputs"] == str(d)
+    assert sorted(os.listdir(d)) == ["g.npy", "h.npy"]
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    img = torch.rand((bench.ROWS, bench.COLS), generator=torch.Generator(device="cuda").manual_seed(1234), device="cuda", dtype=torch.float32)
+    g, h = cv.SteerableFiltersG2(None, 4, 0.67).setup_steer(img, bench.THETA, flags=cv.SETUP_BASIS)
+    rows = bench._dump_rows()
+    for name, want in (("g", g), ("h", h)):
+        got = np.load(d / (name + ".npy"))
+        assert got.dtype == np.float32 and got.shape == (len(rows), bench.COLS)
+        assert np.array_equal(got, want.cpu().numpy()[rows]), name
+
+
 def test_bench_two_ranks_with_the_secondary_legs_and_a_crashing_rank(tmp_path):
     """the N > 1 rehearsal WITH the secondary legs (round-2 verdict: the rehearsal passed --no-extra): both ranks on device 0,
     gloo for the collectives, every leg that does not need an RCCL communicator runs with its barriers and its

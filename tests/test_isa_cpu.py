@@ -5,7 +5,6 @@ and warns about -- a clobber of it, so the compiler cannot be TOLD.  What makes 
 in front of an instruction that reads it, and that these kernels contain no such instruction.  This test keeps that true across
 compiler versions and edits: in the assembly of every strip kernel, every instruction that mentions M0 must be one of the two our own
 statements emit, and every LDS-DMA load must sit directly behind such a write plus its wait state."""
-import hashlib
 import os
 import re
 import subprocess
@@ -17,20 +16,17 @@ SRC = os.path.join(ROOT, "cvsteer_amd", "csrc")
 HIPCC = "/opt/rocm/bin/hipcc"
 
 
-def _assembly():
-    files = [os.path.join(SRC, n) for n in ("cvs_kernels_basis.hip", "cvs_internal.h", "cvs_device_math.h")]
-    key = hashlib.sha1(b"".join(open(f, "rb").read() for f in files)).hexdigest()[:16]
-    path = "/tmp/cvs_basis_isa_%s.s" % key
-    if not os.path.exists(path):
-        subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-I" + os.path.join(ROOT, "include"),
-                        "-I" + SRC, "-S", "--cuda-device-only", files[0], "-o", path + ".tmp"], check=True, stderr=subprocess.DEVNULL)
-        os.replace(path + ".tmp", path)
+def _assembly(out_dir):
+    """this tree's kernels as compiled by this machine's hipcc, into a directory of the test session"""
+    path = os.path.join(str(out_dir), "cvs_kernels_basis.s")
+    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-I" + os.path.join(ROOT, "include"),
+                    "-I" + SRC, "-S", "--cuda-device-only", os.path.join(SRC, "cvs_kernels_basis.hip"), "-o", path], check=True, stderr=subprocess.DEVNULL)
     return open(path).read()
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
-def test_m0_is_touched_by_nothing_but_the_lds_dma_statements():
-    text = _assembly()
+def test_m0_is_touched_by_nothing_but_the_lds_dma_statements(tmp_path):
+    text = _assembly(tmp_path)
     kernels = re.findall(r"^(_ZN3cvs\w+):[^\n]*\n(.*?)s_endpgm", text, re.S | re.M)
     assert len(kernels) >= 100, len(kernels)
     ours = re.compile(r"^\s*(s_mov_b32 m0, s\d+|s_add_u32 m0, m0, 0x100)\s*(;.*)?$")
