@@ -128,7 +128,6 @@ int do_setup(cvs_handle h, const cvs_plane* image, unsigned flags, bool steer, f
         a.warm_k = (fresh && !pyr && in_bytes >= ((size_t)24 << 20)) ? (wk >= 0 ? wk : 4) : 0;
     }
     a.nt_stores = use_nt_stores(h, (size_t)a.rows * a.cols);
-    a.diag = h->diag;
     a.out_row_lo = out_row_lo;
     a.out_row_hi = out_row_hi;
     if (steer) {
@@ -889,17 +888,6 @@ int cvs_pipeline_batch(cvs_handle h, const cvs_plane* images, int n, const cvs_p
     h->have_basis = h->have_orient = h->persist != 0;
     return CVS_OK;
 }
-
-#ifdef CVS_DIAG_STAMPS
-// diagnostic builds only: per-wave time stamps of the next basis launches go to `buf` (device memory,
-// 4 x 8 bytes per wave); not declared in the public header
-int cvs_diag_set_buffer(cvs_handle h, void* buf)
-{
-    if (!h) return CVS_E_BADARG;
-    h->diag = static_cast<unsigned long long*>(buf);
-    return CVS_OK;
-}
-#endif
 
 int cvs_select_frame(cvs_handle h, int frame)
 {

@@ -47,7 +47,6 @@ struct cvs_context {
     float* arena = nullptr;
     size_t arena_elems = 0, arena_used = 0;
     float* point_out = nullptr;
-    unsigned long long* diag = nullptr;  // diagnostic builds only
     const void* last_image = nullptr;    // input pointer of the previous setup (fresh-input heuristic)
     int layout = 1;   // CVS_OPT_STATE_LAYOUT: 0 = planar, 1 = row-interleaved (default), 2 = one group of twelve for full G2 setups
     int atan_mode = 0, strip_rows = 0, find_on = 0, block_order = -1, persist = 1, g4_ext = 0, autotune = 1;

@@ -104,9 +104,6 @@ struct BasisArgs {
     // API layer runs the stand-alone k_pyr_down otherwise (identical values).
     float* pyr_out;
     size_t pyr_pitch;          // elements
-    // diagnostic builds only (-DCVS_DIAG_STAMPS, tools/k1_timeline.py): per-wave {start, first store, end}
-    // 100 MHz real-time stamps; never read by the product, nullptr in normal builds
-    unsigned long long* diag;
 };
 
 // basis plane p of a launch, whatever group it is in

@@ -34,7 +34,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
 #include <type_traits>
 #include <utility>
@@ -176,7 +175,7 @@ struct Folded {
 // with a scalar-register operand takes its SIMD for 4.3-4.7 cycles, the same instruction with a literal 2.3-2.5 and goes through beside
 // another wave's (profiles/r05_valu_rate.txt), and the pipeline variants -- plain arithmetic, bound by instruction issue -- spend a quarter of
 // their vector instructions on tap multiplies.  Same operations on the same values in the same order: bit-identical.  The launcher picks
-// the literal instance only when the handle's folded taps equal the table bit for bit (launch_fast_impl).
+// the literal instance only when the handle's folded taps equal the table bit for bit (plan_strips).
 template <class B>
 struct TapsArg {
     const Folded<B>& t;
@@ -289,15 +288,13 @@ __device__ __forceinline__ rsrc_t plane_rsrc(const float* base, size_t bytes)
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0,
                                              (int)(bytes > kMaxPlaneBytes ? kMaxPlaneBytes : bytes), 0x00020000);
 }
-// cache policy of the streaming stores (aux bits of the buffer store on gfx94x / gfx950: 1 = sc0, 2 = nt, 16 = sc1).  nt alone is the
-// product's (the other policies were measured in round 4: profiles/HISTORY_round_4.md); -DCVS_STREAM_AUX=n builds a twin with another one
-#ifndef CVS_STREAM_AUX
-#define CVS_STREAM_AUX 2
-#endif
+// cache policy of the streaming stores (aux bits of the buffer store on gfx94x / gfx950: 1 = sc0, 2 = nt, 16 = sc1): nt alone, the
+// product's since round 4, when nt sc0 and nt sc1 were measured against it (profiles/r04_store_policy_probe.txt, profiles/HISTORY_round_4.md)
+constexpr int kStreamAux = 2;
 template <bool STREAM>
 __device__ __forceinline__ void bst(rsrc_t r, unsigned lane_off, unsigned row_off, float v)
 {
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, lane_off, row_off, STREAM ? CVS_STREAM_AUX : 0);
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, lane_off, row_off, STREAM ? kStreamAux : 0);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -384,9 +381,6 @@ constexpr unsigned kCanary = 0x7fc0dead;   // a quiet NaN with a payload; as an 
 #define CVS_VMW8(a, b, c, d, e, f, g, h) CVS_VMW(a) CVS_VMW(b) CVS_VMW(c) CVS_VMW(d) CVS_VMW(e) CVS_VMW(f) CVS_VMW(g) CVS_VMW(h)
 __device__ __forceinline__ void wait_vmcnt(int n)
 {
-#ifdef CVS_DIAG_NOWAIT   // diagnostic twin only (WRONG results: rows are read before they have landed): what the launches would run at if a wave never had to wait for its
-    n = 63;              // older stores in order to see its row -- an upper bound for any scheme that decouples the input stream from vmcnt
-#endif
 #ifdef CVS_DIAG_CANARY
     n += CVS_DIAG_CANARY_SLACK;
 #endif
@@ -701,17 +695,6 @@ __device__ __forceinline__ void basis_body(const BasisArgs& a, const Folded<B>& 
     const int wv = threadIdx.x >> 6;
     const int x0 = (bx * WPB + wv) * 64;
     if (x0 >= a.cols) return;  // wave-uniform; between two tiles the waves of a workgroup do not wait for each other
-#ifdef CVS_DIAG_STAMPS
-    unsigned long long* stamp = a.diag ? a.diag + ((size_t)(by * a.grid_x + bx) * WPB + wv) * 4 : nullptr;
-    [[maybe_unused]] bool stamped_first = false;
-    if (stamp && lane == 0) {
-        stamp[0] = __builtin_amdgcn_s_memrealtime();
-        stamp[3] = __builtin_amdgcn_s_getreg(20 | (3 << 11)) & 7u;  // HW_REG_XCC_ID[3:0]: the XCD this wave runs on
-    }
-#ifdef CVS_DIAG_CLOCK
-    const unsigned long long clk0 = __builtin_amdgcn_s_memtime();  // shader-clock ticks; stamp[1] then holds the ticks this wave lived
-#endif
-#endif
     // Planes of 2 GiB and more are filtered in row bands, one launch per band: the host shifts every plane
     // pointer down by row_base rows, so that the 32-bit buffer offsets of the band (halo included) stay
     // below 2 GiB, and the launch covers output rows [row_lo, row_hi).  Such planes never fit the
@@ -985,11 +968,6 @@ __device__ __forceinline__ void basis_body(const BasisArgs& a, const Folded<B>& 
 #ifdef CVS_DIAG_CANARY
                 const unsigned st_row0 = st_tally;
 #endif
-#ifdef CVS_DIAG_STAMPS
-#ifndef CVS_DIAG_CLOCK
-                if (stamp && !stamped_first) { stamped_first = true; if (lane == 0) stamp[1] = __builtin_amdgcn_s_memrealtime(); }
-#endif
-#endif
                 // outputs-only batch: pitch, mask and plane offsets of the outputs are read from the kernel arguments HERE, a column pass and an
                 // epilogue ahead of the stores that use them (read at the stores, every row waited for the scalar cache), and not kept across rows
                 [[maybe_unused]] unsigned b2_pitch_b = 0, b2_mask = 0, b2_off[8] = {};
@@ -1094,39 +1072,38 @@ __device__ __forceinline__ void basis_body(const BasisArgs& a, const Folded<B>& 
         atomicAdd(&g_canary[3], (unsigned long long)cn_rows);
     }
 #endif
-#ifdef CVS_DIAG_STAMPS
-    if (stamp && lane == 0) {
-        __builtin_amdgcn_s_waitcnt(0);
-        stamp[2] = __builtin_amdgcn_s_memrealtime();
-#ifdef CVS_DIAG_CLOCK
-        stamp[1] = __builtin_amdgcn_s_memtime() - clk0;
-#endif
-    }
-#endif
 }
 
 #undef CVS_BST
+// The prologue of the single-bank strip kernels: the tile of this workgroup (pick_tile) and, in a batch, its frame z; false = none.
+// Frame batches with state kept: the frames are dispatched dealt from z_ways equal parts of the batch in turn (0, n/2, 1,
+// n/2 + 1, ... for two), so that the frames in flight together -- about ten of 1080p -- have their state planes, inputs and
+// outputs in DISTANT parts of the batch's blocks: planes written together stream faster when they come from two runs of the
+// VRAM allocator than from one, and a 3 GB batch block spans more than one run.  profiles/r03_batch_ways_probe.txt, 32 x 1080p, same handles and buffers: a "slow" block 0.677 -> 0.752 of the HBM
+// roofline, a "fast" one 0.717 -> 0.725; four / eight / sixteen parts give less (0.72 / 0.71 / 0.70).
+template <int BATCH>
+__device__ __forceinline__ bool pick_frame_tile(const BasisArgs& a, int* s_tile, int& bx, int& by, unsigned& z)
+{
+    if (!pick_tile(a, s_tile, bx, by, z)) return false;
+    if constexpr (BATCH != 0) {
+        if (a.z_ways > 1) {
+            const unsigned per = ((unsigned)a.batch + a.z_ways - 1) / a.z_ways;
+            z = (z % a.z_ways) * per + z / a.z_ways;
+            if (z >= (unsigned)a.batch) return false;
+        }
+    }
+    return true;
+}
+
 // (BasisArgs must stay the FIRST parameter of both strip kernels: kernarg_fresh() reads it at offset 0 of the kernel-argument segment)
 template <class B, int FLAGS, bool STREAM, int BATCH = 0, bool ONE = false, int WPB = 4, bool U8 = false>
 __global__ __launch_bounds__(64 * WPB, B::MIN_WAVES) void k_basis(const BasisArgs a, const Folded<B> t)
 {
     __shared__ float lds[WPB][(2 * B::W + 2) * kRingLine];   // per wave: a ring of 2W+1 lines + one spare line (dma_warm)
     __shared__ int s_tile;
-    // Frame batches with state kept: the frames are dispatched dealt from z_ways equal parts of the batch in turn (0, n/2, 1,
-    // n/2 + 1, ... for two), so that the frames in flight together -- about ten of 1080p -- have their state planes, inputs and
-    // outputs in DISTANT parts of the batch's blocks: planes written together stream faster when they come from two runs of the
-    // VRAM allocator than from one, and a 3 GB batch block spans more than one run.  profiles/r03_batch_ways_probe.txt, 32 x 1080p, same handles and buffers: a "slow" block 0.677 -> 0.752 of the HBM
-    // roofline, a "fast" one 0.717 -> 0.725; four / eight / sixteen parts give less (0.72 / 0.71 / 0.70).
     int bx = 0, by = 0;
     unsigned z = 0;
-    if (!pick_tile(a, &s_tile, bx, by, z)) return;
-    if constexpr (BATCH != 0) {
-        if (a.z_ways > 1) {
-            const unsigned per = ((unsigned)a.batch + a.z_ways - 1) / a.z_ways;
-            z = (z % a.z_ways) * per + z / a.z_ways;
-            if (z >= (unsigned)a.batch) return;
-        }
-    }
+    if (!pick_frame_tile<BATCH>(a, &s_tile, bx, by, z)) return;
     basis_body<B, FLAGS, STREAM, BATCH, ONE, WPB, U8>(a, t, lds[threadIdx.x >> 6], z, bx, by);
 }
 
@@ -1140,14 +1117,7 @@ __global__ __launch_bounds__(256, B::MIN_WAVES) void k_basis_lit(const BasisArgs
     __shared__ int s_tile;
     int bx = 0, by = 0;
     unsigned z = 0;
-    if (!pick_tile(a, &s_tile, bx, by, z)) return;
-    if constexpr (BATCH != 0) {   // (frames dealt from z_ways parts of the batch: see k_basis)
-        if (a.z_ways > 1) {
-            const unsigned per = ((unsigned)a.batch + a.z_ways - 1) / a.z_ways;
-            z = (z % a.z_ways) * per + z / a.z_ways;
-            if (z >= (unsigned)a.batch) return;
-        }
-    }
+    if (!pick_frame_tile<BATCH>(a, &s_tile, bx, by, z)) return;
     basis_body<B, FLAGS, STREAM, BATCH, true, 4, U8, true>(a, t, lds[threadIdx.x >> 6], z, bx, by);
 }
 
@@ -1276,11 +1246,7 @@ bool basis_may_need_scratch(int kind, int width, const float (*taps)[kMaxTaps], 
 // that every XCD gets the same number
 static unsigned dynamic_blocks(size_t ntiles, int* dyn_static)
 {
-    constexpr int pct = 25;
-    int tail_pct = 10;
-#ifdef CVS_DIAG_STAMPS   // diagnostic twin only (tools/k1_timeline.py): how long a tail balances the XCDs, and what that is worth
-    if (const char* e = std::getenv("CVS_DIAG_TAIL_PCT")) tail_pct = std::max(1, std::min(100, std::atoi(e)));
-#endif
+    constexpr int pct = 25, tail_pct = 10;
     const size_t tail = std::max<size_t>(8, ntiles * tail_pct / 100);
     const size_t stat = ntiles > tail ? (ntiles - tail) / 8 * 8 : 0;
     *dyn_static = (int)stat;
@@ -1325,59 +1291,89 @@ static hipError_t dynamic_queues(BasisArgs& a, hipStream_t s, bool* captured)
     if (a.tile_parity) *a.tile_parity ^= 1;
     return hipSuccess;
 }
-static hipError_t dynamic_queues_done(const BasisArgs& a, hipStream_t s, bool captured, hipError_t launched)
+
+// a strip launch bracketed by the queue handling of the dynamic order (dynamic_queues; under capture the reset launch behind it):
+// `launch(a)` gets the launch's own copy of the arguments
+template <class L>
+static hipError_t with_queues(const BasisArgs& a_in, hipStream_t s, L&& launch)
 {
-    if (launched != hipSuccess || !captured) return launched;
+    BasisArgs a = a_in;
+    bool captured = false;
+    const hipError_t qe = dynamic_queues(a, s, &captured);
+    if (qe != hipSuccess) return qe;
+    const hipError_t e = launch(a);
+    if (e != hipSuccess || !captured) return e;
     hipLaunchKernelGGL(k_reset_queues, dim3(1), dim3(64), 0, s, a.tile_ctr);
     return hipGetLastError();
 }
 
-template <class B>
-static hipError_t launch_fast_impl(BasisArgs& a, const Folded<B>& f, hipStream_t s)
+// how one strip launch runs (plan_strips)
+struct StripPlan {
+    dim3 grid, block;
+    unsigned lds;   // dynamic LDS nobody touches: the BasisArgs::wg_per_cu cap
+    bool banded;    // a row band of a launch split by for_each_band
+    bool one;       // the single-resource form (ONE)
+    bool lit;       // the taps are the reference's defaults: the pipeline variants take k_basis_lit
+};
+
+// The plan of one strip launch, from its arguments after banding: the grid and the variant choices, and the launcher's fields of `a`
+// (grid_x, grid_y, dyn_nz, dyn_static, warm_bands, the final warm_k, z_ways, the normalised block_order).  `bank`: the folded taps of a
+// single-bank launch (the G2 bank: k_basis, k_basis_lit); nullptr = the G4 pair launch (k_basis_pair).
+static StripPlan plan_strips(BasisArgs& a, const Folded<BankG2>* bank)
 {
+    using B = BankG2;
+    constexpr int wpb = 4;   // waves per workgroup
+    const bool pair = bank == nullptr;
+    StripPlan p{};
+    p.block = dim3(64 * wpb);
     const int strips_x = (a.cols + 63) / 64;
-    const bool orient_v = a.orient != nullptr && B::KIND == 2;
-    constexpr int wpb = 4;
-    dim3 grid((strips_x + wpb - 1) / wpb, (a.row_hi - a.row_lo + a.strip_rows - 1) / a.strip_rows);
-    a.grid_x = grid.x;
-    a.grid_y = grid.y;
-    a.dyn_nz = 1;
+    a.grid_x = (strips_x + wpb - 1) / wpb;
+    a.grid_y = (a.row_hi - a.row_lo + a.strip_rows - 1) / a.strip_rows;
     a.warm_bands = a.warm_k > 0 ? (a.grid_y + a.warm_k) / (a.warm_k + 1) : 0;
-    if (a.grid_y < 10 || a.frames) a.warm_k = 0;   // (frame batches: warm_k is set by the API layer only where it pays)
+    // no read-ahead under ten bands; the single-bank launch none for table batches either (frame batches: warm_k is set by the API
+    // layer only where it pays)
+    if (a.grid_y < 10 || (!pair && a.frames)) a.warm_k = 0;
     if (a.block_order == kOrderDynamic && !a.tile_ctr) a.block_order = 0;   // no queue slot for this handle: the plain order
     if (a.block_order != kOrderDynamic && a.block_order != kOrderXcdColumns) a.block_order = 0;
-    const bool dyn = a.block_order == kOrderDynamic;
-    // dynamic order: the grid is set at the launch itself (CVS_LAUNCH_K): it covers the frames of a batch as well
-    if (a.block_order == kOrderXcdColumns) grid = dim3(8u * (unsigned)(((a.grid_x + 7) / 8) * a.grid_y), 1);
-    dim3 block(64 * wpb);
-    const bool orient = orient_v;
-    const bool steer = a.steer_g != nullptr && a.steer_h != nullptr;
+    // planes of tiles (grid.z): the pair launch's two half banks, or a batch's frames -- dealt from z_ways parts, the grid a
+    // multiple of z_ways (slots past the batch leave at once: pick_frame_tile)
+    unsigned nz = 1;
+    if (pair) {
+        nz = 2;
+    } else if (a.frames || a.batch_regular) {
+        if (a.z_ways < 1 || a.z_ways > a.batch) a.z_ways = 1;
+        nz = (unsigned)((a.batch + a.z_ways - 1) / a.z_ways * a.z_ways);
+    }
+    a.dyn_nz = (int)nz;
+    if (a.block_order == kOrderDynamic)   // one row of workgroups over all z-planes; pick_tile deals the tiles
+        p.grid = dim3(dynamic_blocks((size_t)a.grid_x * a.grid_y * nz, &a.dyn_static));
+    else if (a.block_order == kOrderXcdColumns)
+        p.grid = dim3(8u * (unsigned)(((a.grid_x + 7) / 8) * a.grid_y), 1, nz);
+    else
+        p.grid = dim3(a.grid_x, a.grid_y, nz);
     // the single-resource form addresses the whole image from row 0: a banded launch (a caller plane of 2 GiB or
     // more beside a small state block, e.g. a narrow column view of a huge image) must use the per-plane form,
     // which honours row_lo / row_hi / row_base
-    const bool banded = a.row_lo != 0 || a.row_hi != a.rows || a.row_base != 0;
-    const bool one = !banded && a.state_bytes > 0 && a.state_bytes <= kMaxPlaneBytes;
+    p.banded = a.row_lo != 0 || a.row_hi != a.rows || a.row_base != 0;
+    p.one = !p.banded && a.state_bytes > 0 && a.state_bytes <= kMaxPlaneBytes;
+    if (pair) return p;   // the pair launch has no literal-tap instance and never pads LDS
     // the handle's taps are the reference's defaults, bit for bit: the pipeline variants run the instance with the taps compiled in
-    bool lit = false;
-    if constexpr (B::KIND == 2 && B::HALF == 0) {
-        lit = a.lit_taps != 0;
-        for (int m = 0; m < B::NTP && lit; ++m)
-            for (int i = 0; i <= B::W && lit; ++i)
-            {   // (through plain floats: __builtin_bit_cast on an element of the vector type reads element 0 whatever the index -- seen with this compiler)
-                const float ex = f.tp[m][i].x, oy = f.tp[m][i].y;
-                unsigned ue, uo;
-                std::memcpy(&ue, &ex, sizeof ue);
-                std::memcpy(&uo, &oy, sizeof uo);
-                lit = ue == kLitEvenG2[B::te(m)][i] && uo == kLitOddG2[B::to(m)][i];
-            }
-    }
-    if (a.lit_used) *a.lit_used = 0;   // set where such an instance is launched (CVS_LAUNCH_U)
+    // (single-resource form only)
+    p.lit = p.one && a.lit_taps != 0;
+    for (int m = 0; m < B::NTP && p.lit; ++m)
+        for (int i = 0; i <= B::W && p.lit; ++i)
+        {   // (through plain floats: __builtin_bit_cast on an element of the vector type reads element 0 whatever the index -- seen with this compiler)
+            const float ex = bank->tp[m][i].x, oy = bank->tp[m][i].y;
+            unsigned ue, uo;
+            std::memcpy(&ue, &ex, sizeof ue);
+            std::memcpy(&uo, &oy, sizeof uo);
+            p.lit = ue == kLitEvenG2[B::te(m)][i] && uo == kLitOddG2[B::to(m)][i];
+        }
     // BasisArgs::wg_per_cu: the launch asks for more LDS than it uses, so that at most that many workgroups share a CU (see cvs_tune.cpp)
-    unsigned lds_pad = 0;
     if (a.wg_per_cu > 0 && a.wg_per_cu < 8) {
         constexpr unsigned kLds = 160u << 10, kStatic = (unsigned)(wpb * (2 * B::W + 2) * kRingLine * sizeof(float) + 64);
         const unsigned n = (unsigned)a.wg_per_cu, want = (kLds / n + kLds / (n + 1)) / 2;   // N fit, N + 1 do not: the middle of that interval
-        lds_pad = want > kStatic ? want - kStatic : 0;
+        p.lds = want > kStatic ? want - kStatic : 0;
         // never more than a workgroup may have (one or two per CU would ask for 120 / 67 KiB): the cap is then weaker than asked for
         static const unsigned max_lds = [] {
             int dev = 0, v = 0;
@@ -1385,157 +1381,100 @@ static hipError_t launch_fast_impl(BasisArgs& a, const Folded<B>& f, hipStream_t
             (void)hipGetLastError();
             return 64u << 10;
         }();
-        if (kStatic + lds_pad > max_lds) lds_pad = max_lds > kStatic ? max_lds - kStatic : 0;
+        if (kStatic + p.lds > max_lds) p.lds = max_lds > kStatic ? max_lds - kStatic : 0;
     }
-#define CVS_LAUNCH_K(...)                                                                  \
-    do {                                                                                   \
-        if (dyn) {                                                                         \
-            a.dyn_nz = (int)grid.z;                                                        \
-            grid = dim3(dynamic_blocks((size_t)a.grid_x * a.grid_y * grid.z, &a.dyn_static), 1, 1); \
-        }                                                                                  \
-        hipLaunchKernelGGL((__VA_ARGS__), grid, block, lds_pad, s, a, f);         \
-    } while (0)
-#define CVS_LAUNCH_U(FL, BATCHED, WP, U)                                                   \
-    do {                                                                                   \
-        if constexpr (B::KIND == 2 && B::HALF == 0 && ((FL) & F_PIPE) != 0 && (BATCHED) != 1) {   \
-            if (lit && one) {                                                              \
-                if (a.lit_used) *a.lit_used = 1;                                           \
-                if (a.nt_stores) CVS_LAUNCH_K(k_basis_lit<B, FL, true, BATCHED, U>);       \
-                else CVS_LAUNCH_K(k_basis_lit<B, FL, false, BATCHED, U>);                  \
-                break;                                                                     \
-            }                                                                              \
-        }                                                                                  \
-        if (one) {                                                                         \
-            if (a.nt_stores) CVS_LAUNCH_K(k_basis<B, FL, true, BATCHED, true, WP, U>);     \
-            else CVS_LAUNCH_K(k_basis<B, FL, false, BATCHED, true, WP, U>);                \
-        } else {                                                                           \
-            if (a.nt_stores) CVS_LAUNCH_K(k_basis<B, FL, true, BATCHED, false, WP, U>);    \
-            else CVS_LAUNCH_K(k_basis<B, FL, false, BATCHED, false, WP, U>);               \
-        }                                                                                  \
-    } while (0)
-#define CVS_LAUNCH_W(FL, BATCHED, WP)                       \
-    do {                                                    \
-        if (a.in_u8) CVS_LAUNCH_U(FL, BATCHED, WP, true);   \
-        else CVS_LAUNCH_U(FL, BATCHED, WP, false);          \
-    } while (0)
-#define CVS_LAUNCH_B(FL, BATCHED) CVS_LAUNCH_W(FL, BATCHED, 4)
-#define CVS_LAUNCH(FL) CVS_LAUNCH_B(FL, 0)
-    if (a.frames || a.batch_regular) {  // batched caller pipeline: one launch, grid.z = frames (G2 only)
-        if constexpr (B::KIND == 2 && B::HALF == 0) {
-            grid.z = a.batch;
-            if (a.z_ways < 1 || a.z_ways > a.batch) a.z_ways = 1;
-            if (a.z_ways > 1) grid.z = (unsigned)((a.batch + a.z_ways - 1) / a.z_ways * a.z_ways);   // slots past the batch leave at once
-            if (a.batch_regular && a.out_one) {
-                // exactly the three feature maps of find*(magnitude, phase) with the compatible arctangent: the specialised instance
-                const bool feat3 = a.no_state && a.out_mask == 0xE0u && !a.find_on_e && a.atan_mode == 0;
-                if (feat3) CVS_LAUNCH_B(F_ORIENT | F_PIPE | F_NOSTATE | F_FEAT3, 2);
-                else if (a.no_state) CVS_LAUNCH_B(F_ORIENT | F_PIPE | F_NOSTATE, 2);
-                else CVS_LAUNCH_B(F_ORIENT | F_PIPE, 2);
+    return p;
+}
+
+// run-time flags as compile-time ones: f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...)
+template <class F>
+static void with_bools(F&& f)
+{
+    f();
+}
+template <class F, class... R>
+static void with_bools(F&& f, bool b, R... rest)
+{
+    if (b) with_bools([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else with_bools([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+
+template <int FL, int BATCH = 0>
+struct Variant {
+    static constexpr int flags = FL, batch = BATCH;
+};
+
+// The instance (FLAGS, BATCH) of a single-bank launch: f(Variant<FLAGS, BATCH>{}).  false = none fits, nothing launched.
+template <class F>
+static bool with_variant(const BasisArgs& a, bool banded, F&& f)
+{
+    const bool orient = a.orient != nullptr, steer = a.steer_g != nullptr && a.steer_h != nullptr, pipe = orient && a.pipe;
+    // BATCH 2: a regular batch with one output resource per frame; 1: any other batch (a frame table, or outputs anywhere)
+    const bool batch2 = a.batch_regular && a.out_one;
+    // exactly the three feature maps of find*(magnitude, phase) with the compatible arctangent: the specialised instance (FEAT3).
+    // The outputs that exist: out_mask in a BATCH 2 launch, the pipe_out entries of a single image; BATCH 1 has no such instance.
+    bool feat3 = a.no_state && !a.find_on_e && a.atan_mode == 0;
+    if (batch2) feat3 = feat3 && a.out_mask == 0xE0u;
+    else for (int k = 0; k < 8; ++k) feat3 = feat3 && ((a.pipe_out[k].p != nullptr) == (k >= 5));
+    auto pipeline = [&](auto batch) {
+        constexpr int BATCH = decltype(batch)::value;
+        if constexpr (BATCH != 1) {
+            if (feat3) return f(Variant<F_ORIENT | F_PIPE | F_NOSTATE | F_FEAT3, BATCH>{});
+        }
+        if (a.no_state) return f(Variant<F_ORIENT | F_PIPE | F_NOSTATE, BATCH>{});
+        return f(Variant<F_ORIENT | F_PIPE, BATCH>{});
+    };
+    if (a.frames || a.batch_regular) {   // batched caller pipeline: one launch, grid.z = frames
+        if (batch2) pipeline(std::integral_constant<int, 2>{});
+        else pipeline(std::integral_constant<int, 1>{});
+    } else if (a.pyr_out) {   // filter this pyramid level and write the next one (launch_basis has checked that the launch qualifies)
+        if (banded || pipe || steer) return false;
+        if (orient) f(Variant<F_ORIENT | F_PYR>{});
+        else f(Variant<F_PYR>{});
+    } else if (pipe) {   // (steer weights beside the pipeline are not used)
+        pipeline(std::integral_constant<int, 0>{});
+    } else if (orient) {
+        if (steer) f(Variant<F_ORIENT | F_STEER>{});
+        else f(Variant<F_ORIENT>{});
+    } else {
+        if (steer) f(Variant<F_STEER>{});
+        else f(Variant<0>{});
+    }
+    return true;
+}
+
+// the G2 bank in one launch: k_basis, or k_basis_lit
+static hipError_t launch_bank(BasisArgs& a, const Folded<BankG2>& f, hipStream_t s)
+{
+    using B = BankG2;
+    const StripPlan p = plan_strips(a, &f);
+    if (a.lit_used) *a.lit_used = 0;
+    const bool ok = with_variant(a, p.banded, [&](auto v) {
+        constexpr int FL = decltype(v)::flags, BATCH = decltype(v)::batch;
+        with_bools([&](auto stream, auto one, auto u8, auto lit) {
+            constexpr bool ST = decltype(stream)::value, ONE = decltype(one)::value, U8 = decltype(u8)::value;
+            // k_basis_lit: the whole G2 bank's pipeline variants in the single-resource form, table batches (BATCH 1) excepted
+            if constexpr (decltype(lit)::value && ONE && (FL & F_PIPE) != 0 && BATCH != 1) {
+                if (a.lit_used) *a.lit_used = 1;
+                hipLaunchKernelGGL((k_basis_lit<B, FL, ST, BATCH, U8>), p.grid, p.block, p.lds, s, a, f);
             } else {
-                if (a.no_state) CVS_LAUNCH_B(F_ORIENT | F_PIPE | F_NOSTATE, 1);
-                else CVS_LAUNCH_B(F_ORIENT | F_PIPE, 1);
+                hipLaunchKernelGGL((k_basis<B, FL, ST, BATCH, ONE, 4, U8>), p.grid, p.block, p.lds, s, a, f);
             }
-            return hipGetLastError();
-        } else {
-            return hipErrorInvalidValue;
-        }
-    }
-    const bool pipe = orient && a.pipe;
-    const int flags = pipe ? (F_ORIENT | F_PIPE) : ((orient ? F_ORIENT : 0) | (steer ? F_STEER : 0));
-    if (a.pyr_out) {  // filter this pyramid level and write the next one (launch_basis has checked that the launch qualifies)
-        if constexpr (B::KIND == 2 && B::HALF == 0) {
-            if (banded || pipe || steer) return hipErrorInvalidValue;
-            if (orient) CVS_LAUNCH(F_ORIENT | F_PYR);
-            else CVS_LAUNCH(F_PYR);
-            return hipGetLastError();
-        } else {
-            return hipErrorInvalidValue;
-        }
-    }
-    if constexpr (B::KIND == 2) {
-        switch (flags) {
-            case 0: CVS_LAUNCH(0); break;
-            case F_ORIENT: CVS_LAUNCH(F_ORIENT); break;
-            case F_STEER: CVS_LAUNCH(F_STEER); break;
-            case F_ORIENT | F_STEER: CVS_LAUNCH(F_ORIENT | F_STEER); break;
-            default: {
-                bool feat3 = a.no_state && !a.find_on_e && a.atan_mode == 0;
-                for (int k = 0; k < 8; ++k) feat3 = feat3 && ((a.pipe_out[k].p != nullptr) == (k >= 5));
-                if (feat3) CVS_LAUNCH(F_ORIENT | F_PIPE | F_NOSTATE | F_FEAT3);
-                else if (a.no_state) CVS_LAUNCH(F_ORIENT | F_PIPE | F_NOSTATE);
-                else CVS_LAUNCH(F_ORIENT | F_PIPE);
-                break;
-            }
-        }
-    } else {
-        return hipErrorInvalidValue;   // G4 runs as the pair launch (launch_pair)
-    }
-#undef CVS_LAUNCH_B
-#undef CVS_LAUNCH_W
-#undef CVS_LAUNCH_U
-#undef CVS_LAUNCH_K
-#undef CVS_LAUNCH
+        }, a.nt_stores != 0, p.one, a.in_u8 != 0, p.lit);
+    });
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
+}
+
+// the G4 bank as its two half banks in one launch (k_basis_pair; blockIdx.z = half bank): plain filter, or with the fused steer
+static hipError_t launch_pair(BasisArgs& a, const Folded<BankG4G>& fg, const Folded<BankG4H>& fh, hipStream_t s)
+{
+    const StripPlan p = plan_strips(a, nullptr);
+    with_bools([&](auto steer, auto stream, auto one, auto u8) {
+        constexpr int FL = decltype(steer)::value ? F_STEER : 0;
+        hipLaunchKernelGGL((k_basis_pair<BankG4G, BankG4H, FL, decltype(stream)::value, decltype(one)::value, decltype(u8)::value>), p.grid,
+                           p.block, p.lds, s, a, fg, fh);
+    }, a.steer_g != nullptr && a.steer_h != nullptr, a.nt_stores != 0, p.one, a.in_u8 != 0);
     return hipGetLastError();
-}
-
-template <class B>
-static hipError_t launch_fast(const BasisArgs& a_in, const Folded<B>& f, hipStream_t s)
-{
-    BasisArgs a = a_in;
-    bool captured = false;
-    const hipError_t qe = dynamic_queues(a, s, &captured);
-    if (qe != hipSuccess) return qe;
-    return dynamic_queues_done(a, s, captured, launch_fast_impl<B>(a, f, s));
-}
-
-template <class BG, class BH>
-static hipError_t launch_pair_impl(BasisArgs& a, const Folded<BG>& fg, const Folded<BH>& fh, hipStream_t s)
-{
-    const int strips_x = (a.cols + 63) / 64;
-    dim3 grid((strips_x + 3) / 4, (a.row_hi - a.row_lo + a.strip_rows - 1) / a.strip_rows, 2), block(256);
-    a.grid_x = grid.x;
-    a.grid_y = grid.y;
-    a.dyn_nz = 2;
-    a.warm_bands = a.warm_k > 0 ? (a.grid_y + a.warm_k) / (a.warm_k + 1) : 0;
-    if (a.grid_y < 10) a.warm_k = 0;
-    if (a.block_order == kOrderDynamic && !a.tile_ctr) a.block_order = 0;
-    if (a.block_order != kOrderDynamic && a.block_order != kOrderXcdColumns) a.block_order = 0;
-    const bool dyn = a.block_order == kOrderDynamic;
-    // dynamic order: the grid is set at the launch (see launch_fast); tiles of both half banks share the queues
-    if (a.block_order == kOrderXcdColumns) grid = dim3(8u * (unsigned)(((a.grid_x + 7) / 8) * a.grid_y), 1, 2);
-    const bool steer = a.steer_g != nullptr && a.steer_h != nullptr;
-    const bool banded = a.row_lo != 0 || a.row_hi != a.rows || a.row_base != 0;  // see launch_fast
-    const bool one = !banded && a.state_bytes > 0 && a.state_bytes <= kMaxPlaneBytes;
-#define CVS_PAIR_K(...)                                                                                         \
-    do {                                                                                                        \
-        if (dyn) grid = dim3(dynamic_blocks((size_t)a.grid_x * a.grid_y * 2, &a.dyn_static), 1, 1);             \
-        hipLaunchKernelGGL((__VA_ARGS__), grid, block, 0, s, a, fg, fh);                         \
-    } while (0)
-#define CVS_PAIR(FL, ST, ON)                                                      \
-    do {                                                                          \
-        if (a.in_u8) CVS_PAIR_K(k_basis_pair<BG, BH, FL, ST, ON, true>);          \
-        else CVS_PAIR_K(k_basis_pair<BG, BH, FL, ST, ON, false>);                 \
-    } while (0)
-    if (steer) {
-        if (a.nt_stores) { if (one) CVS_PAIR(F_STEER, true, true); else CVS_PAIR(F_STEER, true, false); }
-        else { if (one) CVS_PAIR(F_STEER, false, true); else CVS_PAIR(F_STEER, false, false); }
-    } else {
-        if (a.nt_stores) { if (one) CVS_PAIR(0, true, true); else CVS_PAIR(0, true, false); }
-        else { if (one) CVS_PAIR(0, false, true); else CVS_PAIR(0, false, false); }
-    }
-#undef CVS_PAIR
-#undef CVS_PAIR_K
-    return hipGetLastError();
-}
-
-template <class BG, class BH>
-static hipError_t launch_pair(const BasisArgs& a_in, const Folded<BG>& fg, const Folded<BH>& fh, hipStream_t s)
-{
-    BasisArgs a = a_in;
-    bool captured = false;
-    const hipError_t qe = dynamic_queues(a, s, &captured);
-    if (qe != hipSuccess) return qe;
-    return dynamic_queues_done(a, s, captured, launch_pair_impl<BG, BH>(a, fg, fh, s));
 }
 
 static hipError_t launch_generic(int kind, int width, const float (*taps)[kMaxTaps], const BasisArgs& a,
@@ -1654,12 +1593,10 @@ bool launch_pyr_strip(const float* src, size_t spitch, int rows, int cols, float
     a.row_lo = 0;
     a.row_hi = rows;
     a.row_base = 0;
-    const int strips_x = (cols + 63) / 64;
-    dim3 grid((strips_x + 3) / 4, (rows + a.strip_rows - 1) / a.strip_rows), block(256);
-    a.grid_x = grid.x;
-    a.grid_y = grid.y;
+    // the march's plan: its own 46-row strips, the plain order (block_order 0, no queues), plain stores, no state block (not ONE), no LDS pad
     Folded<BankG2> f{};
-    hipLaunchKernelGGL((k_basis<BankG2, F_PYR | F_PYRONLY, false, 0, false, 4>), grid, block, 0, s, a, f);
+    const StripPlan p = plan_strips(a, &f);
+    hipLaunchKernelGGL((k_basis<BankG2, F_PYR | F_PYRONLY, false, 0, false, 4>), p.grid, p.block, p.lds, s, a, f);
     *err = hipGetLastError();
     return true;
 }
@@ -1704,7 +1641,7 @@ hipError_t launch_basis(int kind, int width, const float (*taps)[kMaxTaps], cons
         BasisArgs b = a;
         b.row_lo = b.row_base = 0;
         b.row_hi = b.rows;
-        return launch_fast<BankG2>(b, f, s);
+        return with_queues(b, s, [&](BasisArgs& q) { return launch_bank(q, f, s); });
     }
     if (a.pyr_out && !basis_fuses_pyr(kind, width, taps, a)) {  // not a launch the fused form covers: two launches, same values
         BasisArgs b = a;
@@ -1718,13 +1655,14 @@ hipError_t launch_basis(int kind, int width, const float (*taps)[kMaxTaps], cons
     if (!fast_geometry_ok(a, width) || band_rows(a, width) == 0) return launch_generic(kind, width, taps, a, scratch, s);
     if (kind == 2 && width == BankG2::W) {
         Folded<BankG2> f;
-        if (fold_taps<BankG2>(taps, f)) return for_each_band(a, width, [&](const BasisArgs& b) { return launch_fast<BankG2>(b, f, s); });
+        if (fold_taps<BankG2>(taps, f))
+            return for_each_band(a, width, [&](const BasisArgs& b) { return with_queues(b, s, [&](BasisArgs& q) { return launch_bank(q, f, s); }); });
     }
     if (kind == 4 && width == BankG4G::W) {
         Folded<BankG4G> fg;
         Folded<BankG4H> fh;
         if (fold_taps<BankG4G>(taps, fg) && fold_taps<BankG4H>(taps, fh))
-            return for_each_band(a, width, [&](const BasisArgs& b) { return launch_pair<BankG4G, BankG4H>(b, fg, fh, s); });
+            return for_each_band(a, width, [&](const BasisArgs& b) { return with_queues(b, s, [&](BasisArgs& q) { return launch_pair(q, fg, fh, s); }); });
     }
     return launch_generic(kind, width, taps, a, scratch, s);
 }
