@@ -338,56 +338,16 @@ class SteerableFilters:
         return dst
 
 
-class SteerableFiltersG2(SteerableFilters):
-    """fa::SteerableFiltersG2 (SteerableFiltersG2.h:35-67)."""
+class _CallerPipeline:
+    """The callers' sequence (test/test.cpp:85-90, example/steer.cpp:86-122) on a SteerableFilters object: find*, the fused
+    pipeline for one image or a batch of frames, and the 8-bit conversions.  Shared by G2 and -- with extensions on -- G4."""
 
-    KIND = L.KIND_G2
-    DEFAULT_WIDTH = 4
-    DEFAULT_SPACING = 0.67
-    _DEFAULT_FLAGS = SETUP_FULL
-
-    def getDominantOrientationAngle(self):
-        return self._state(L.PLANE_THETA)
-
-    def getDominantOrientationStrength(self):
-        return self._state(L.PLANE_STRENGTH)
-
-    def coefficients(self):
-        """(C1, C2, C3) -- the reference's protected m_c1..m_c3"""
-        return tuple(self._state(w) for w in (L.PLANE_C1, L.PLANE_C2, L.PLANE_C3))
-
-    def steer_point(self, p, theta, full=False):
-        """steer(const cv::Point& p, theta, ...): p = (x, y) = (col, row)"""
-        out = (C.c_float * 5)()
-        self._check(lib().cvs_steer_point(self._h, int(p[0]), int(p[1]), float(theta), out), "cvs_steer_point")
-        vals = tuple(float(v) for v in out)
-        return vals if full else vals[:2]
-
-    def computeMagnitudeAndPhase(self, g2, h2):
-        mag, phase = self._new_like(g2), self._new_like(g2)
-        self._bind_stream(g2, h2, mag, phase)
-        pg, ph, pm, pp = _plane(g2), _plane(h2), _plane(mag), _plane(phase)
-        self._check(lib().cvs_mag_phase(self._h, C.byref(pg), C.byref(ph), C.byref(pm), C.byref(pp)), "cvs_mag_phase")
-        return mag, phase
-
-    def wrap(self, angle):
-        """SteerableFilters::wrap (SteerableFilters.cpp:46-51)"""
-        out = self._new_like(angle)
-        self._bind_stream(angle, out)
-        pa, po = _plane(angle), _plane(out)
-        self._check(lib().cvs_wrap(self._h, C.byref(pa), C.byref(po)), "cvs_wrap")
-        return out
-
-    def phaseWeights(self, phase, phi, signum, k=2.0):
-        lam = self._new_like(phase)
-        self._bind_stream(phase, lam)
-        pp, pl = _plane(phase), _plane(lam)
-        self._check(lib().cvs_phase_weights(self._h, C.byref(pp), C.byref(pl), float(phi), int(bool(signum)), float(k)),
-                    "cvs_phase_weights")
-        return lam
+    def _caller_check(self, where):
+        """raises CvsError(E_UNSUPPORTED) where the object has no caller pipeline"""
 
     def find(self, e, phase, which=(True, True, True)):
         """findEdges + findDarkLines + findBrightLines in one pass -> (edges, dark, bright)"""
+        self._caller_check("cvs_find")
         outs = [self._new_like(e) if w else None for w in which]
         self._bind_stream(e, phase, *[o for o in outs if o is not None])
         pe, pp = _plane(e), _plane(phase)
@@ -407,7 +367,7 @@ class SteerableFiltersG2(SteerableFilters):
 
     def pipeline(self, image, out=None):
         """the callers' whole sequence (test/test.cpp:85-90) for one image ->
-        (g2, h2, e, magnitude, phase, edges, dark, bright)"""
+        (g, h, e, magnitude, phase, edges, dark, bright) -- g2 / h2, or g4 / h4"""
         image = _as_input(image)
         self._like = image
         outs = list(out) if out is not None else self._new_block_like(image, 8)
@@ -420,7 +380,7 @@ class SteerableFiltersG2(SteerableFilters):
 
     def pipeline_batch(self, frames, out=None, outputs=None):
         """pipeline() for n same-size frames in one launch.  frames: [n, H, W] tensor/array (or a list
-        of planes).  outputs: indices into (g2, h2, e, magnitude, phase, edges, dark, bright) to
+        of planes).  outputs: indices into (g, h, e, magnitude, phase, edges, dark, bright) to
         produce (default all 8); returns / fills out [n, len(outputs), H, W].  select_frame(i) then
         picks whose state the getters and steer() use (unless set_persist(False))."""
         sel = list(range(8)) if outputs is None else [int(k) for k in outputs]
@@ -469,12 +429,15 @@ class SteerableFiltersG2(SteerableFilters):
     def set_persist(self, on):
         """pipeline()/pipeline_batch(): keep the basis + orientation planes (default, like the reference
         object) or write the requested outputs only"""
+        self._caller_check("set_persist")
         self.set_option(L.OPT_PERSIST_STATE, 1 if on else 0)
 
     def select_frame(self, i):
+        self._caller_check("cvs_select_frame")
         self._check(lib().cvs_select_frame(self._h, int(i)), "cvs_select_frame")
 
     def _to_u8(self, plane, gain):
+        self._caller_check("cvs_normalize_u8" if gain is None else "cvs_convert_u8")
         self._bind_stream(plane)
         pp = _plane(plane)
         if _is_torch(plane) and plane.is_cuda:
@@ -499,13 +462,63 @@ class SteerableFiltersG2(SteerableFilters):
         return self._to_u8(plane, gain)
 
 
-class SteerableFiltersG4(SteerableFilters):
+class SteerableFiltersG2(_CallerPipeline, SteerableFilters):
+    """fa::SteerableFiltersG2 (SteerableFiltersG2.h:35-67)."""
+
+    KIND = L.KIND_G2
+    DEFAULT_WIDTH = 4
+    DEFAULT_SPACING = 0.67
+    _DEFAULT_FLAGS = SETUP_FULL
+
+    def getDominantOrientationAngle(self):
+        return self._state(L.PLANE_THETA)
+
+    def getDominantOrientationStrength(self):
+        return self._state(L.PLANE_STRENGTH)
+
+    def coefficients(self):
+        """(C1, C2, C3) -- the reference's protected m_c1..m_c3"""
+        return tuple(self._state(w) for w in (L.PLANE_C1, L.PLANE_C2, L.PLANE_C3))
+
+    def steer_point(self, p, theta, full=False):
+        """steer(const cv::Point& p, theta, ...): p = (x, y) = (col, row)"""
+        out = (C.c_float * 5)()
+        self._check(lib().cvs_steer_point(self._h, int(p[0]), int(p[1]), float(theta), out), "cvs_steer_point")
+        vals = tuple(float(v) for v in out)
+        return vals if full else vals[:2]
+
+    def computeMagnitudeAndPhase(self, g2, h2):
+        mag, phase = self._new_like(g2), self._new_like(g2)
+        self._bind_stream(g2, h2, mag, phase)
+        pg, ph, pm, pp = _plane(g2), _plane(h2), _plane(mag), _plane(phase)
+        self._check(lib().cvs_mag_phase(self._h, C.byref(pg), C.byref(ph), C.byref(pm), C.byref(pp)), "cvs_mag_phase")
+        return mag, phase
+
+    def wrap(self, angle):
+        """SteerableFilters::wrap (SteerableFilters.cpp:46-51)"""
+        out = self._new_like(angle)
+        self._bind_stream(angle, out)
+        pa, po = _plane(angle), _plane(out)
+        self._check(lib().cvs_wrap(self._h, C.byref(pa), C.byref(po)), "cvs_wrap")
+        return out
+
+    def phaseWeights(self, phase, phi, signum, k=2.0):
+        lam = self._new_like(phase)
+        self._bind_stream(phase, lam)
+        pp, pl = _plane(phase), _plane(lam)
+        self._check(lib().cvs_phase_weights(self._h, C.byref(pp), C.byref(pl), float(phi), int(bool(signum)), float(k)),
+                    "cvs_phase_weights")
+        return lam
+
+class SteerableFiltersG4(_CallerPipeline, SteerableFilters):
     """fa::SteerableFiltersG4 (SteerableFiltersG4.h:35-57): setup + steer only.
 
     extensions=True switches on what the reference leaves unfinished (G4.h:55, G4.cpp:88-90): dominant
     orientation / strength / C1..C3 derived from the G4/H4 steering polynomials, steer(..., full=True)
-    and a working computeMagnitudeAndPhase.  Off by default: then the class behaves exactly like the
-    reference (empty getters, no-op computeMagnitudeAndPhase)."""
+    and a working computeMagnitudeAndPhase, and the callers' sequence of G2 -- find*, pipeline / pipeline_batch
+    (outputs g4, h4, e, magnitude, phase, edges, dark, bright), set_persist, select_frame, normalize_u8 / convert_u8.
+    Off by default: then the class behaves exactly like the reference (empty getters, no-op computeMagnitudeAndPhase)
+    and the caller methods raise CvsError(E_UNSUPPORTED)."""
 
     KIND = L.KIND_G4
     DEFAULT_WIDTH = 6
@@ -521,6 +534,10 @@ class SteerableFiltersG4(SteerableFilters):
                 self._setup_flags = SETUP_FULL
         if image is not None:
             self.setup(image)
+
+    def _caller_check(self, where):
+        if not self.extensions:
+            raise CvsError(L.E_UNSUPPORTED, where, "the G4 caller pipeline is an extension (extensions=True)")
 
     def getDominantOrientationAngle(self):
         """never assigned in the reference (G4.h:55): an empty Mat -- unless extensions are on"""

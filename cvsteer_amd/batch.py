@@ -195,6 +195,11 @@ class NativeBatch:
     def set_persist(self, on):
         self._check(_L.lib().cvs_batch_set_option(self._b, _L.OPT_PERSIST_STATE, 1 if on else 0), "cvs_batch_set_option")
 
+    def set_g4_extensions(self, on):
+        """CVS_OPT_G4_EXTENSIONS on every rank: a batch made with kind=KIND_G4 then runs the G4 caller pipeline
+        (outputs g4, h4, e, magnitude, phase, edges, dark, bright); without it run() raises CvsError(E_UNSUPPORTED)"""
+        self._check(_L.lib().cvs_batch_set_option(self._b, _L.OPT_G4_EXTENSIONS, 1 if on else 0), "cvs_batch_set_option")
+
     # -- config 4 --
     def run(self, frames, n_frames, frame_shape, outputs=(5, 6, 7), out=None, root=0, gather=True, self_via_transport=False):
         """frames: [n_frames, H, W] float32 CUDA tensor on the root (None elsewhere), or a numpy array of that shape

@@ -255,6 +255,90 @@ int steer_common(cvs_handle h, bool map, float theta, const cvs_plane* theta_map
     return finish(c);
 }
 
+// G4 caller pipeline (CVS_OPT_G4_EXTENSIONS), second stage: the pair launches have written the basis planes of `nframes` frames
+// from the current frame on; ONE per-pixel launch (k_g4_pipeline, blockIdx.z = frame) writes the orientation planes (state kept
+// only) and the requested outputs -- outs[k] is frame 0's plane k, frame z's lies out_fstride elements further (device planes;
+// host planes only with nframes = 1).  The values are those of setup(FULL) + steer_map(NULL, ...) + find(...), bit for bit.
+int g4_pipe_stage(cvs_handle h, const cvs_plane* const outs[8], int nframes, size_t out_fstride)
+{
+    Call c;
+    int rc = begin(h, c, {outs[0], outs[1], outs[2], outs[3], outs[4], outs[5], outs[6], outs[7]});
+    if (rc) return rc;
+    G4PipeArgs a{};
+    a.rows = h->rows;
+    a.cols = h->cols;
+    a.frames = nframes;
+    a.atan_mode = h->atan_mode;
+    a.find_on_e = h->find_on;
+    for (int p = 0; p < h->nb; ++p) {
+        const PlaneRef r = state_ref(h, p);
+        a.in[p] = {r.p, r.pitch, h->frame_stride};
+    }
+    if (h->persist) {   // c1, c2, c3, theta, strength: the state setup(FULL) leaves behind
+        for (int i = 0; i < 5; ++i) {
+            const PlaneRef r = state_ref(h, h->nb + i);
+            a.out[G4P_C1 + i] = {r.p, r.pitch, h->frame_stride};
+        }
+    }
+    for (int k = 0; k < 8; ++k) {
+        PlaneRef r;
+        if ((rc = out_ref(c, outs[k], r))) return rc;
+        a.out[G4P_G + k] = {r.p, r.pitch, out_fstride};
+    }
+    a.nt_stores = use_nt_stores(h, (size_t)a.rows * a.cols * nframes);
+    a.nt_loads = a.nt_stores;   // the basis planes of an image that large are not cache-resident and are read once here
+    HIP_TRY(h, launch_g4_pipeline(a, h->stream));
+    // CVS_OPT_PERSIST_STATE = 0: the basis planes were scratch for this call, nothing addressable is left
+    h->have_basis = h->have_orient = h->persist != 0;
+    return finish(c);
+}
+
+// one G4 image (frame `frame` of `nframes`): the pair launch of a basis-only setup -- the tuner key of cvs_setup(BASIS) -- and the stage
+int g4_pipeline_one(cvs_handle h, const cvs_plane* image, const cvs_plane* const outs[8], int nframes, int frame)
+{
+    const int rc = do_setup(h, image, CVS_SETUP_BASIS, false, 0.f, nullptr, nullptr, nullptr, nframes, frame);
+    return rc ? rc : g4_pipe_stage(h, outs, 1, 0);
+}
+
+// G4 frame batch (cvs_pipeline_batch, arguments checked).  f32 device frames whose outputs lie at one constant frame stride (an
+// [n, K, H, W] block, the usual case): one pair launch per frame, each writing its frame's state block, then ONE per-pixel launch
+// over all frames.  Anything else -- host or 8-bit frames, outputs anywhere -- goes frame by frame.
+int g4_pipeline_frames(cvs_handle h, const cvs_plane* images, int n, const cvs_plane* outs, bool all_dev)
+{
+    auto frame_outs = [&](int i, const cvs_plane* po[8]) {
+        for (int k = 0; k < 8; ++k) po[k] = (outs && outs[(size_t)i * 8 + k].data) ? &outs[(size_t)i * 8 + k] : nullptr;
+    };
+    bool block = all_dev;
+    ptrdiff_t d_out = 0;
+    bool have_stride = false;
+    for (int i = 1; i < n && block; ++i)
+        for (int k = 0; k < 8 && block && outs; ++k) {
+            const cvs_plane &o0 = outs[k], &oi = outs[(size_t)i * 8 + k];
+            if ((o0.data == nullptr) != (oi.data == nullptr)) block = false;
+            else if (o0.data) {
+                const ptrdiff_t dk = oi.data - o0.data;
+                if (!have_stride) { d_out = dk / i; have_stride = true; }
+                block = dk == d_out * i && d_out > 0 && oi.step == o0.step;   // (a stride of 0 would have every frame write the same planes)
+            }
+        }
+    int rc;
+    if (!block) {
+        for (int i = 0; i < n; ++i) {
+            const cvs_plane* po[8];
+            frame_outs(i, po);
+            if ((rc = g4_pipeline_one(h, &images[i], po, n, i))) return rc;
+        }
+        h->cur_frame = 0;
+        return CVS_OK;
+    }
+    for (int i = 0; i < n; ++i)
+        if ((rc = do_setup(h, &images[i], CVS_SETUP_BASIS, false, 0.f, nullptr, nullptr, nullptr, n, i))) return rc;
+    h->cur_frame = 0;
+    const cvs_plane* po[8];
+    frame_outs(0, po);
+    return g4_pipe_stage(h, po, n, (size_t)d_out);
+}
+
 }  // namespace
 
 extern "C" {
@@ -702,12 +786,16 @@ int cvs_find(cvs_handle h, const cvs_plane* e, const cvs_plane* phase, const cvs
 int cvs_pipeline(cvs_handle h, const cvs_plane* image, const cvs_plane* const outs[8])
 {
     if (!h || !outs) return CVS_E_BADARG;
-    if (h->kind != CVS_KIND_G2) return fail(h, CVS_E_UNSUPPORTED, "the caller pipeline exists for G2 only");
+    if (h->kind != CVS_KIND_G2 && !h->g4_ext) return fail(h, CVS_E_UNSUPPORTED, "the caller pipeline exists for G2, and for G4 with CVS_OPT_G4_EXTENSIONS");
     int rc = check_plane(h, image, "image", true);
     if (rc) return rc;
     for (int o = 0; o < 8; ++o) {
         if (!outs[o]) continue;
         if ((rc = check_plane(h, outs[o], "out")) || (rc = check_same(h, outs[o], image->rows, image->cols))) return rc;
+    }
+    if (h->kind == CVS_KIND_G4) {   // the pair launch, then one per-pixel launch over its 11 planes
+        if ((rc = check_no_overlap(h, image, outs, 8))) return rc;
+        return g4_pipeline_one(h, image, outs, 1, 0);
     }
     // one launch: filter bank, orientation and the whole caller sequence in the kernel's epilogue
     return do_setup(h, image, CVS_SETUP_FULL, false, 0.f, nullptr, nullptr, outs);
@@ -716,7 +804,7 @@ int cvs_pipeline(cvs_handle h, const cvs_plane* image, const cvs_plane* const ou
 int cvs_pipeline_batch(cvs_handle h, const cvs_plane* images, int n, const cvs_plane* outs)
 {
     if (!h || !images || n < 1) return CVS_E_BADARG;
-    if (h->kind != CVS_KIND_G2) return fail(h, CVS_E_UNSUPPORTED, "the caller pipeline exists for G2 only");
+    if (h->kind != CVS_KIND_G2 && !h->g4_ext) return fail(h, CVS_E_UNSUPPORTED, "the caller pipeline exists for G2, and for G4 with CVS_OPT_G4_EXTENSIONS");
     int rc;
     const int rows = images[0].rows, cols = images[0].cols;
     bool all_dev = true;
@@ -738,6 +826,7 @@ int cvs_pipeline_batch(cvs_handle h, const cvs_plane* images, int n, const cvs_p
             if ((rc = check_no_overlap(h, &images[i], po, 8))) return rc;
         }
     }
+    if (h->kind == CVS_KIND_G4) return g4_pipeline_frames(h, images, n, outs, all_dev);
     // 8-bit frames that lie back to back on the device (a driver's upload of a block of byte images): the one-launch path
     // below reads the bytes itself (BasisArgs::in_u8), like any regular f32 batch -- no widened copy
     bool u8_batch = n >= 1 && images[0].mem == (CVS_MEM_DEVICE | CVS_DEPTH_U8);

@@ -131,6 +131,7 @@ struct Slot {
 
 struct cvs_batch_context {
     int kind = 0, width = 0, world = 0, transport = TRANSPORT_NONE;
+    int g4_ext = 0;           // CVS_OPT_G4_EXTENSIONS as last set on every rank's handle (the caller pipeline for a G4 batch)
     float spacing = 0.f;
     float u8_gain = 0.f;      // 8-bit host outputs: 0 = normalize(0, 255, MINMAX) per map, > 0 = convertTo(CV_8U, gain)
     std::vector<Slot> slots;  // local ranks, ascending
@@ -838,13 +839,13 @@ int cvs_batch_set_option(cvs_batch b, int option, int value)
 {
     if (!b) return CVS_E_BADARG;
     for (Slot& s : b->slots) B_CVS(b, s.h, cvs_set_option(s.h, option, value));
+    if (option == CVS_OPT_G4_EXTENSIONS) b->g4_ext = value;
     return CVS_OK;
 }
 
 int cvs_batch_run(cvs_batch b, const cvs_batch_cfg* cfg, const cvs_plane* inputs, const cvs_plane* outputs, cvs_batch_timing* timing)
 {
     if (!b || !cfg) return CVS_E_BADARG;
-    if (b->kind != CVS_KIND_G2) return fail(b, CVS_E_UNSUPPORTED, "the caller pipeline exists for G2 only");
     const int rows = cfg->rows, cols = cfg->cols, F = cfg->n_frames, root = cfg->root;
     if (rows <= 0 || cols <= 0 || F < 1) return fail(b, CVS_E_SIZE, "empty batch");
     if (root < 0 || root >= b->world) return fail(b, CVS_E_BADARG, "root");
@@ -863,8 +864,10 @@ int cvs_batch_run(cvs_batch b, const cvs_batch_cfg* cfg, const cvs_plane* inputs
     auto lfail = [&](int code, const char* what) {
         if (local_rc == CVS_OK) local_rc = fail(b, code, what);
     };
+    // (a rank of a multi-process world whose handles lack the option must not leave its peers waiting: agreed on below)
+    if (b->kind != CVS_KIND_G2 && !b->g4_ext) lfail(CVS_E_UNSUPPORTED, "the caller pipeline exists for G2, and for G4 with CVS_OPT_G4_EXTENSIONS");
     bool host = false;
-    if (rs) {
+    if (rs && local_rc == CVS_OK) {
         if (!inputs) lfail(CVS_E_BADARG, "the root rank needs the input frames");
         else if (cfg->gather && !outputs) lfail(CVS_E_BADARG, "the root rank needs output planes to gather into");
         else if ((inputs[0].mem & 0xff) == CVS_MEM_HOST) {

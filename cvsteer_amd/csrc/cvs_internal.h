@@ -157,6 +157,26 @@ struct PointArgs {
 };
 
 hipError_t launch_point(PointOp op, const PointArgs& a, hipStream_t s);
+
+// ---- G4 caller pipeline (extension, CVS_OPT_G4_EXTENSIONS): the per-pixel stage behind the pair launch ----
+// One launch reads the 11 basis planes and writes any of: the five orientation planes, then the callers' sequence at the
+// G4 dominant angle -- exactly OP_G4_ORIENT, OP_G4_STEER_MAP (theta = that angle) and OP_FIND composed, bit for bit.
+// Frame z of a batch (blockIdx.z) addresses plane + z * frame_stride.  All pitches / strides in elements.
+struct FramePlane {
+    float* p;             // nullptr = not requested (outputs)
+    size_t pitch;
+    size_t frame_stride;
+};
+enum { G4P_C1 = 0, G4P_C2, G4P_C3, G4P_THETA, G4P_STRENGTH, G4P_G, G4P_H, G4P_E, G4P_MAG, G4P_PHASE, G4P_EDGES, G4P_DARK, G4P_BRIGHT, G4P_NOUT };
+struct G4PipeArgs {
+    int rows, cols, frames;
+    FramePlane in[11];        // g4a..g4e, h4a..h4f
+    FramePlane out[G4P_NOUT];
+    int atan_mode;
+    int find_on_e;            // 1 = find*(e, phase), 0 = find*(magnitude, phase)
+    int nt_stores, nt_loads;
+};
+hipError_t launch_g4_pipeline(const G4PipeArgs& a, hipStream_t s);
 // single-pixel steer (G2.cpp:115-134): uses a.w, a.c2t, a.s2t; writes {g2,h2,e,mag,phase} to out5 (device)
 hipError_t launch_steer_point(const float* basis, size_t plane_stride, size_t offset, const float* orient, size_t orient_stride,
                               size_t orient_offset, const PointArgs& a, float* out5, hipStream_t s);   // orient may be nullptr

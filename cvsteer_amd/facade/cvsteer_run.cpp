@@ -1,11 +1,13 @@
 // cvsteer_run.cpp -- `cvsteer-run` for MI355X: the reference's batch driver (example/steer.cpp:59-173) in C++ over
 // the C ABI (include/cvsteer_hip.h).  Host side only: no HIP call is made here.
 //
-//   cvsteer-run --input <image | list.txt> --output <dir> [--gain G] [--gpus N | --devices a,b,..] [--ext .pgm|.npy] [--verbose]
+//   cvsteer-run --input <image | list.txt> --output <dir> [--gain G] [--gpus N | --devices a,b,..] [--ext .pgm|.npy] [--g4] [--verbose]
 //
 // Per image the reference's per-file body (steer.cpp:69-124): gray f32 (unscaled 0..255) -> SteerableFiltersG2(gray, 4,
 // 0.67) -> steer at the dominant orientation -> findEdges / findDarkLines / findBrightLines on the magnitude -> 8-bit
-// via normalize(0, 255, MINMAX) or convertTo(gain) -> <base>_edges, <base>_lines_dark, <base>_lines_bright.
+// via normalize(0, 255, MINMAX) or convertTo(gain) -> <base>_edges, <base>_lines_dark, <base>_lines_bright.  --g4: the same
+// sequence on the G4/H4 bank (width 6, spacing 0.5, CVS_OPT_G4_EXTENSIONS = 1: steered at the G4 dominant orientation -- an
+// extension, the reference's G4 class has no orientation or find*).
 // Where the reference runs cv::parallel_for_ over the files (steer.cpp:169), this driver hands runs of equally sized
 // images to cvs_batch_run as HOST planes: every GPU uploads its own block of frames over its own link, filters it in
 // one fused launch per chunk, turns the three feature maps into bytes on the device (8-bit host output planes of
@@ -228,7 +230,7 @@ int main(int argc, char** argv)
     float gain = 0.f;
     int gpus = 1, max_batch = 64;
     std::vector<int> device_list;
-    bool verbose = false;
+    bool verbose = false, g4 = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto val = [&]() -> std::string {
@@ -248,9 +250,10 @@ int main(int argc, char** argv)
         }
         else if (a == "--ext") ext = val();
         else if (a == "--max-batch") max_batch = std::max(1, std::atoi(val().c_str()));
+        else if (a == "--g4") g4 = true;   // the G4/H4 bank, width 6, spacing 0.5, extensions on (its caller pipeline is an extension)
         else if (a == "--verbose" || a == "-v") verbose = true;
         else if (a == "--help" || a == "-h") {
-            std::printf("usage: cvsteer-run --input <image | list.txt> --output <dir> [--gain G] [--gpus N | --devices a,b,..] [--ext .pgm|.npy] [--verbose]\n");
+            std::printf("usage: cvsteer-run --input <image | list.txt> --output <dir> [--gain G] [--gpus N | --devices a,b,..] [--ext .pgm|.npy] [--g4] [--verbose]\n");
             return 0;
         } else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
@@ -261,7 +264,12 @@ int main(int argc, char** argv)
         const std::vector<std::string> files = input_list(input);
         std::vector<int> devices(gpus);
         for (int d = 0; d < gpus; ++d) devices[d] = device_list.empty() ? d : device_list[d];
-        CHECK_BATCH(batch, cvs_batch_create_local(CVS_KIND_G2, 4, 0.67f, gpus, devices.data(), &batch), "cvs_batch_create_local");
+        if (g4) {
+            CHECK_BATCH(batch, cvs_batch_create_local(CVS_KIND_G4, 6, 0.5f, gpus, devices.data(), &batch), "cvs_batch_create_local");
+            CHECK_BATCH(batch, cvs_batch_set_option(batch, CVS_OPT_G4_EXTENSIONS, 1), "cvs_batch_set_option");
+        } else {
+            CHECK_BATCH(batch, cvs_batch_create_local(CVS_KIND_G2, 4, 0.67f, gpus, devices.data(), &batch), "cvs_batch_create_local");
+        }
         CHECK_BATCH(batch, cvs_batch_set_option(batch, CVS_OPT_PERSIST_STATE, 0), "cvs_batch_set_option");  // only the three maps are kept
 
         size_t next = 0;

@@ -1,12 +1,14 @@
 """cvsteer-run for MI355X: the reference's batch driver (example/steer.cpp:59-173) over the HIP engine.
 
-    python -m cvsteer_amd.run --input <image | list.txt> --output <dir> [--gain G]
+    python -m cvsteer_amd.run --input <image | list.txt> --output <dir> [--gain G] [--g4]
     python -m torch.distributed.run --nproc-per-node 8 -m cvsteer_amd.run --input list.txt --output out
 
 Per image, exactly the reference's per-file body (steer.cpp:69-124): gray f32 (unscaled 0..255) ->
 SteerableFiltersG2(gray, 4, 0.67) -> steer at the dominant orientation -> findEdges / findDarkLines /
 findBrightLines on the magnitude -> 8-bit via normalize(0,255,MINMAX) or convertTo(gain) ->
-<base>_edges.png, <base>_lines_dark.png, <base>_lines_bright.png.  All arithmetic, including the
+<base>_edges.png, <base>_lines_dark.png, <base>_lines_bright.png.  --g4 runs the same sequence on the
+G4/H4 bank instead (SteerableFiltersG4(gray, 6, 0.5) with extensions on: steered at the G4 dominant
+orientation -- an extension, the reference's G4 class has no orientation or find*).  All arithmetic, including the
 8-bit conversion, runs on the GPU; only file decoding/encoding is host work (Pillow / numpy, since
 OpenCV's imgcodecs are not available).
 
@@ -86,11 +88,12 @@ def main(argv=None):
     ap.add_argument("--output", default="", help="output directory")
     ap.add_argument("--gain", type=float, default=0.0, help="gain for the 8-bit output (0 = min-max normalise)")
     ap.add_argument("--ext", default=".png", help="output file extension (.png, .pgm, .npy ...)")
+    ap.add_argument("--g4", action="store_true", help="the G4/H4 bank (width 6, spacing 0.5, extensions on) instead of G2/H2")
     ap.add_argument("--verbose", action="store_true")
     args = ap.parse_args(argv)
 
     import torch
-    from . import SteerableFiltersG2
+    from . import SteerableFiltersG2, SteerableFiltersG4
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -101,7 +104,10 @@ def main(argv=None):
     lo, hi = shard_range(len(files), world, rank)
     if args.output:
         os.makedirs(args.output, exist_ok=True)
-    engine = SteerableFiltersG2(None, 4, 0.67, device=local_rank)
+    if args.g4:
+        engine = SteerableFiltersG4(None, 6, 0.5, device=local_rank, extensions=True)
+    else:
+        engine = SteerableFiltersG2(None, 4, 0.67, device=local_rank)
     engine.set_persist(False)  # the driver never revisits an image's basis planes
     failed = 0
     for path in files[lo:hi]:

@@ -84,7 +84,8 @@ enum {
                                 (test/test.cpp:88-90), 1 = find*(e, phase) */
     CVS_OPT_G4_EXTENSIONS = 6, /* 0 (default) = G4 exactly as the reference leaves it (no orientation, no e/mag/phase);
                                   1 = EXTENSION beyond the reference: cvs_setup(G4, CVS_SETUP_FULL) fills C1..C3 / theta /
-                                  strength from the G4/H4 steering polynomials, and cvs_steer_* accept e/mag/phase */
+                                  strength from the G4/H4 steering polynomials, cvs_steer_* accept e/mag/phase, and
+                                  cvs_pipeline / cvs_pipeline_batch / cvs_batch_run run the caller sequence for G4 */
     CVS_OPT_BLOCK_ORDER = 8, /* order in which the basis kernel's workgroups take their tiles: -1 (default) = the engine's choice
                                 (row-major, unless its tuner finds one of the others faster for this shape on the caller's own
                                 launches); 0 = row-major; 1000000 = every XCD walks its own range of column blocks;
@@ -252,11 +253,17 @@ int cvs_find(cvs_handle h, const cvs_plane* e, const cvs_plane* phase,
 
 /* the whole caller sequence of test/test.cpp:85-90 / example/steer.cpp:86-90 for one image:
  * setup(FULL) -> steer(theta_dom, g2,h2,e,mag,phase) -> find*(mag|e, phase).
- * outs[8] = {g2, h2, e, magnitude, phase, edges, dark, bright}; any entry may be NULL. */
+ * outs[8] = {g2, h2, e, magnitude, phase, edges, dark, bright}; any entry may be NULL.
+ * G4 with CVS_OPT_G4_EXTENSIONS = 1 (EXTENSION beyond the reference): the same for the G4/H4 bank, outs[8] = {g4, h4, e,
+ * magnitude, phase, edges, dark, bright} -- every value bit-identical to cvs_setup(FULL) -> cvs_steer_map(NULL, ...) ->
+ * cvs_find(magnitude | e, phase) on the same handle, the state afterwards that of cvs_setup(FULL) (or none, with
+ * CVS_OPT_PERSIST_STATE = 0).  Two launches: the G4 pair launch of the basis planes, then one per-pixel pass over them.
+ * G4 without the option: CVS_E_UNSUPPORTED. */
 int cvs_pipeline(cvs_handle h, const cvs_plane* image, const cvs_plane* const outs[8]);
 
 /* The batch axis (example/steer.cpp:69-124,169: one independent pipeline per file): cvs_pipeline for
- * n images of identical size in ONE kernel launch (grid.z = frame).  outs is a flat array of n*8
+ * n images of identical size in ONE kernel launch (grid.z = frame; G4 with CVS_OPT_G4_EXTENSIONS = 1: one pair launch per
+ * frame, then ONE per-pixel launch over all frames -- f32 device frames whose outputs lie at one constant frame stride).  outs is a flat array of n*8
  * planes, frame-major, order {g2,h2,e,magnitude,phase,edges,dark,bright}; an entry with data == NULL
  * is not written (outs == NULL: state only).  The state of every frame is kept; cvs_select_frame
  * picks the frame that cvs_state_plane / cvs_read_state / cvs_steer_* address (default 0).
@@ -331,7 +338,8 @@ int cvs_batch_create_rank(int kind, int width, float spacing, const void* id128,
 int cvs_batch_destroy(cvs_batch b);
 const char* cvs_batch_last_error(cvs_batch b);
 int cvs_batch_info(cvs_batch b, int* world, int* nlocal, int* transport);
-/* cvs_set_option on every engine of the batch (e.g. CVS_OPT_PERSIST_STATE = 0: outputs only) */
+/* cvs_set_option on every engine of the batch (e.g. CVS_OPT_PERSIST_STATE = 0: outputs only; CVS_OPT_G4_EXTENSIONS = 1: a G4
+ * batch runs the G4 caller pipeline of cvs_pipeline -- without it cvs_batch_run on a G4 batch is CVS_E_UNSUPPORTED) */
 int cvs_batch_set_option(cvs_batch b, int option, int value);
 /* BASELINE config 4 -- the loop of example/steer.cpp:169 over the node: inputs = n_frames dense f32 device planes on the
  * root, outputs = n_frames * 8 planes on the root, frame-major, order of cvs_pipeline (entries not selected by
