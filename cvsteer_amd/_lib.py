@@ -36,7 +36,8 @@ class CvsError(RuntimeError):
 class LaunchInfo(C.Structure):
     """struct cvs_launch_info"""
     _fields_ = [("struct_size", C.c_uint32), ("block_order", C.c_int32), ("strip_rows", C.c_int32), ("nt_stores", C.c_int32),
-                ("state_layout", C.c_int32), ("warm", C.c_int32), ("tuning_launches", C.c_int32), ("tuned", C.c_int32), ("tune_state", C.c_int32), ("wg_per_cu", C.c_int32), ("literal_taps", C.c_int32)]
+                ("state_layout", C.c_int32), ("warm", C.c_int32), ("tuning_launches", C.c_int32), ("tuned", C.c_int32), ("tune_state", C.c_int32), ("wg_per_cu", C.c_int32), ("literal_taps", C.c_int32),
+                ("u8_out", C.c_int32)]
 
 
 _PP = C.POINTER(Plane)
@@ -77,6 +78,8 @@ SIGNATURES = {
     "cvs_find": (C.c_int, [C.c_void_p, _PP, _PP, _PP, _PP, _PP]),
     "cvs_pipeline": (C.c_int, [C.c_void_p, _PP, C.POINTER(_PP)]),
     "cvs_pipeline_batch": (C.c_int, [C.c_void_p, _PP, C.c_int, _PP]),
+    "cvs_set_u8_gain": (C.c_int, [C.c_void_p, C.c_float]),
+    "cvs_get_u8_gain": (C.c_int, [C.c_void_p, _FP]),
     "cvs_select_frame": (C.c_int, [C.c_void_p, C.c_int]),
     "cvs_num_frames": (C.c_int, [C.c_void_p, _IP]),
     "cvs_pyr_down": (C.c_int, [C.c_void_p, _PP, _PP]),

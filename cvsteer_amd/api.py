@@ -365,12 +365,41 @@ class _CallerPipeline:
     def findBrightLines(self, e, phase, k=2.0):
         return self.find(e, phase, (False, False, True))[2]
 
-    def pipeline(self, image, out=None):
+    def _u8_dtype(self, dtype):
+        """dtype=None / float32: f32 outputs; uint8 (torch or numpy): 8-bit outputs (set_u8_gain says how they are made)"""
+        if dtype is None or dtype is np.float32 or (torch is not None and dtype is torch.float32) or dtype == np.float32:
+            return False
+        if dtype is np.uint8 or (torch is not None and dtype is torch.uint8) or dtype == np.uint8:
+            return True
+        raise ValueError("pipeline outputs are float32 or uint8, not %r" % (dtype,))
+
+    def _new_u8_planes(self, like, n):
+        if _is_torch(like) and like.is_cuda:
+            return list(torch.empty((n,) + tuple(like.shape), dtype=torch.uint8, device=like.device))
+        return [np.empty(like.shape, np.uint8) for _ in range(n)]
+
+    def set_u8_gain(self, gain):
+        """8-bit pipeline outputs: 0 (default) = normalize(0, 255, NORM_MINMAX, CV_8UC1) per map, > 0 = convertTo(CV_8UC1, gain)
+        (example/steer.cpp:92-104); negative or NaN raises CvsError(E_BADARG)"""
+        self._check(lib().cvs_set_u8_gain(self._h, float(gain)), "cvs_set_u8_gain")
+
+    def u8_gain(self):
+        v = C.c_float(0.0)
+        self._check(lib().cvs_get_u8_gain(self._h, C.byref(v)), "cvs_get_u8_gain")
+        return v.value
+
+    def pipeline(self, image, out=None, dtype=None):
         """the callers' whole sequence (test/test.cpp:85-90) for one image ->
-        (g, h, e, magnitude, phase, edges, dark, bright) -- g2 / h2, or g4 / h4"""
+        (g, h, e, magnitude, phase, edges, dark, bright) -- g2 / h2, or g4 / h4.  uint8 `out` planes (or dtype=uint8) receive the maps as
+        bytes, made as set_u8_gain says."""
         image = _as_input(image)
         self._like = image
-        outs = list(out) if out is not None else self._new_block_like(image, 8)
+        if out is not None:
+            outs = list(out)
+        elif self._u8_dtype(dtype):
+            outs = self._new_u8_planes(image, 8)
+        else:
+            outs = self._new_block_like(image, 8)
         self._bind_stream(image, *[o for o in outs if o is not None])
         pi = _plane(image)
         planes = [_plane(o) if o is not None else None for o in outs]
@@ -378,16 +407,18 @@ class _CallerPipeline:
         self._check(lib().cvs_pipeline(self._h, C.byref(pi), arr), "cvs_pipeline")
         return tuple(outs)
 
-    def pipeline_batch(self, frames, out=None, outputs=None):
+    def pipeline_batch(self, frames, out=None, outputs=None, dtype=None):
         """pipeline() for n same-size frames in one launch.  frames: [n, H, W] tensor/array (or a list
         of planes).  outputs: indices into (g, h, e, magnitude, phase, edges, dark, bright) to
-        produce (default all 8); returns / fills out [n, len(outputs), H, W].  select_frame(i) then
+        produce (default all 8); returns / fills out [n, len(outputs), H, W] -- float32, or uint8 (a uint8 `out`, or dtype=uint8:
+        8-bit maps as set_u8_gain says).  select_frame(i) then
         picks whose state the getters and steer() use (unless set_persist(False))."""
         sel = list(range(8)) if outputs is None else [int(k) for k in outputs]
+        u8 = self._u8_dtype(dtype)
         block = _is_torch(frames) and frames.dim() == 3 and frames.dtype in (torch.float32, torch.uint8) and frames.is_cuda
         if block and out is None:
-            out = torch.empty((frames.shape[0], len(sel)) + tuple(frames.shape[1:]), dtype=torch.float32, device=frames.device)
-        if block and _is_torch(out) and out.dim() == 4 and out.is_cuda and out.dtype == torch.float32 \
+            out = torch.empty((frames.shape[0], len(sel)) + tuple(frames.shape[1:]), dtype=torch.uint8 if u8 else torch.float32, device=frames.device)
+        if block and _is_torch(out) and out.dim() == 4 and out.is_cuda and out.dtype in (torch.float32, torch.uint8) \
                 and out.shape[0] == frames.shape[0] and out.shape[1] == len(sel) and frames.stride(2) == 1 and out.stride(3) == 1:
             # one [n, H, W] block in, one [n, K, H, W] block out: the plane descriptors are filled in arithmetically
             # (two numpy arrays laid out like `struct cvs_plane`), not one Python object per plane
@@ -400,10 +431,12 @@ class _CallerPipeline:
             imgs["rows"], imgs["cols"], imgs["step"] = rows, cols, frames.stride(1) * esz
             imgs["mem"] = L.MEM_DEVICE | (L.DEPTH_U8 if esz == 1 else 0)
             outs = np.zeros((n, 8), _PLANE_DTYPE)  # data == NULL means "not requested"
-            frame_off = np.arange(n, dtype=np.uint64) * np.uint64(out.stride(0) * 4)
+            osz = 1 if out.dtype == torch.uint8 else 4   # 8-bit outputs: steps in bytes (CVS_DEPTH_U8)
+            frame_off = np.arange(n, dtype=np.uint64) * np.uint64(out.stride(0) * osz)
             for j, k in enumerate(sel):
-                outs["data"][:, k] = out.data_ptr() + frame_off + np.uint64(j * out.stride(1) * 4)
-                outs["rows"][:, k], outs["cols"][:, k], outs["step"][:, k], outs["mem"][:, k] = rows, cols, out.stride(2) * 4, L.MEM_DEVICE
+                outs["data"][:, k] = out.data_ptr() + frame_off + np.uint64(j * out.stride(1) * osz)
+                outs["rows"][:, k], outs["cols"][:, k], outs["step"][:, k] = rows, cols, out.stride(2) * osz
+                outs["mem"][:, k] = L.MEM_DEVICE | (L.DEPTH_U8 if osz == 1 else 0)
             self._check(lib().cvs_pipeline_batch(self._h, imgs.ctypes.data_as(L._PP), n, outs.ctypes.data_as(L._PP)), "cvs_pipeline_batch")
             self._batch_keepalive = (frames, out)
             return out
@@ -413,9 +446,9 @@ class _CallerPipeline:
         shape = tuple(planes[0].shape)
         if out is None:
             if _is_torch(planes[0]):
-                out = torch.empty((n, len(sel)) + shape, dtype=torch.float32, device=planes[0].device)
+                out = torch.empty((n, len(sel)) + shape, dtype=torch.uint8 if u8 else torch.float32, device=planes[0].device)
             else:
-                out = np.empty((n, len(sel)) + shape, np.float32)
+                out = np.empty((n, len(sel)) + shape, np.uint8 if u8 else np.float32)
         self._bind_stream(planes[0], out[0][0])
         imgs = (Plane * n)(*[_plane(p) for p in planes])
         outs = (Plane * (n * 8))()  # zero-initialised: data == NULL means "not requested"

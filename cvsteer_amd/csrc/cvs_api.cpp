@@ -31,9 +31,18 @@ using namespace cvs;
 
 namespace {
 
+// 8-bit outputs of a three-maps launch (BasisArgs::u8_mode): 1 = gain, the output planes are the caller's bytes; 2 = normalise, the
+// outputs are f32 scratch planes and the launch reduces min / max into mm
+struct U8Req {
+    int mode;
+    float gain;
+    int* mm;
+};
+constexpr int kNotFused = 1;   // (internal status: the launch would not take a three-maps instance; nothing was launched)
+
 int do_setup(cvs_handle h, const cvs_plane* image, unsigned flags, bool steer, float theta, const cvs_plane* g,
              const cvs_plane* hq, const cvs_plane* const* pipe_outs = nullptr, int nframes = 1, int frame = 0,
-             int out_row_lo = 0, int out_row_hi = 0, const cvs_plane* pyr = nullptr)
+             int out_row_lo = 0, int out_row_hi = 0, const cvs_plane* pyr = nullptr, const U8Req* u8 = nullptr)
 {
     if (!h) return CVS_E_BADARG;
     int rc = check_plane(h, image, "image", true);
@@ -70,12 +79,17 @@ int do_setup(cvs_handle h, const cvs_plane* image, unsigned flags, bool steer, f
     const cvs_plane* po[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (pipe_outs)
         for (int k = 0; k < 8; ++k) po[k] = pipe_outs[k];
+    const bool u8_bytes = u8 && u8->mode == 1;   // the outputs are the caller's byte planes: nothing to stage for them
     // 8-bit images (what the reference's callers hold: test/test.cpp:73,85, example/steer.cpp:73-86) are read by the strip kernel
     // as bytes: 1 B/pix of input traffic instead of 1 B read + 4 B written by a widening pass + 4 B read
     c.u8_direct = is_u8(image) && !may_generic && !pyr;
     const size_t u8_stage = (c.u8_direct && mem_of(image) == CVS_MEM_HOST) ? u8_stage_elems(image) : 0;
-    rc = begin(h, c, {c.u8_direct ? nullptr : image, steer ? g : nullptr, steer ? hq : nullptr, po[0], po[1], po[2], po[3], po[4], po[5], po[6], po[7], pyr},
-               scratch + u8_stage);
+    if (u8_bytes) {
+        rc = begin(h, c, {c.u8_direct ? nullptr : image}, scratch + u8_stage);
+    } else {
+        rc = begin(h, c, {c.u8_direct ? nullptr : image, steer ? g : nullptr, steer ? hq : nullptr, po[0], po[1], po[2], po[3], po[4], po[5], po[6], po[7], pyr},
+                   scratch + u8_stage);
+    }
     if (rc) return rc;
     // host planes on the fast path of a large enough image: upload, filtering and download overlap band by band
     // (it pays when a sizeable upload can hide behind the downloads: an f32 host image with host outputs -- measured
@@ -143,8 +157,15 @@ int do_setup(cvs_handle h, const cvs_plane* image, unsigned flags, bool steer, f
         a.pipe = 1;
         a.no_state = h->persist ? 0 : 1;
         a.find_on_e = h->find_on;
-        for (int k = 0; k < 8; ++k)
-            if ((rc = out_ref(c, po[k], a.pipe_out[k]))) return rc;
+        for (int k = 0; k < 8; ++k) {
+            if (u8_bytes) a.pipe_out[k] = po[k] ? PlaneRef{po[k]->data, po[k]->step} : PlaneRef{nullptr, 0};   // (pitch in bytes)
+            else if ((rc = out_ref(c, po[k], a.pipe_out[k]))) return rc;
+        }
+        if (u8) {
+            a.u8_mode = u8->mode;
+            a.u8_gain = u8->gain;
+            a.u8_mm = u8->mm;
+        }
     }
     if (pyr) {
         PlaneRef rp;
@@ -159,6 +180,8 @@ int do_setup(cvs_handle h, const cvs_plane* image, unsigned flags, bool steer, f
         h->have_orient = h->have_basis && (flags & CVS_SETUP_ORIENT) != 0;
         return CVS_OK;
     }
+    if (u8 && !basis_u8_fusable(h->kind, h->width, h->taps, a)) return kNotFused;
+    if (u8 && u8->mode == 2) HIP_TRY(h, launch_minmax_init_n(u8->mm, 3, h->stream));
     {
         const bool orient_k = a.orient != nullptr;
         const int variant = (orient_k ? 1 : 0) | (steer ? 2 : 0) | (a.pipe ? 4 : 0) | (a.no_state ? 8 : 0);
@@ -406,10 +429,11 @@ int cvs_destroy(cvs_handle h)
     (void)hipSetDevice(h->device);
     release_state(h);   // no drain: the block is parked with an event
     // staging memory exists only on handles that were given host planes, 8-bit conversions or irregular batches: those wait
-    if (h->arena || h->frame_tab || h->point_out) (void)hipStreamSynchronize(h->stream);
+    if (h->arena || h->frame_tab || h->point_out || h->u8_scr) (void)hipStreamSynchronize(h->stream);
     if (h->arena) (void)hipFree(h->arena);
     if (h->frame_tab) (void)hipFree(h->frame_tab);
     if (h->point_out) (void)hipFree(h->point_out);
+    if (h->u8_scr) (void)hipFree(h->u8_scr);
     if (h->ev_order) (void)hipEventDestroy(h->ev_order);
     for (hipEvent_t e : h->band_ev) (void)hipEventDestroy(e);
     if (h->s_up) (void)hipStreamDestroy(h->s_up);
@@ -783,15 +807,28 @@ int cvs_find(cvs_handle h, const cvs_plane* e, const cvs_plane* phase, const cvs
     return finish(c);
 }
 
+static int pipeline_u8(cvs_handle h, const cvs_plane* images, int n, const cvs_plane* outs, bool batch);
+static int batch_run(cvs_handle h, const cvs_plane* images, int n, const cvs_plane* outs, const U8Req* u8);
+
 int cvs_pipeline(cvs_handle h, const cvs_plane* image, const cvs_plane* const outs[8])
 {
     if (!h || !outs) return CVS_E_BADARG;
     if (h->kind != CVS_KIND_G2 && !h->g4_ext) return fail(h, CVS_E_UNSUPPORTED, "the caller pipeline exists for G2, and for G4 with CVS_OPT_G4_EXTENSIONS");
     int rc = check_plane(h, image, "image", true);
     if (rc) return rc;
+    bool any_u8 = false;
     for (int o = 0; o < 8; ++o) {
         if (!outs[o]) continue;
-        if ((rc = check_plane(h, outs[o], "out")) || (rc = check_same(h, outs[o], image->rows, image->cols))) return rc;
+        if ((rc = check_plane(h, outs[o], "out", true)) || (rc = check_same(h, outs[o], image->rows, image->cols))) return rc;
+        any_u8 = any_u8 || is_u8(outs[o]);
+    }
+    h->last.u8_out = 0;
+    if (any_u8) {
+        if ((rc = check_no_overlap(h, image, outs, 8))) return rc;
+        cvs_plane flat[8] = {};
+        for (int o = 0; o < 8; ++o)
+            if (outs[o]) flat[o] = *outs[o];
+        return pipeline_u8(h, image, 1, flat, false);
     }
     if (h->kind == CVS_KIND_G4) {   // the pair launch, then one per-pixel launch over its 11 planes
         if ((rc = check_no_overlap(h, image, outs, 8))) return rc;
@@ -801,24 +838,22 @@ int cvs_pipeline(cvs_handle h, const cvs_plane* image, const cvs_plane* const ou
     return do_setup(h, image, CVS_SETUP_FULL, false, 0.f, nullptr, nullptr, outs);
 }
 
+
 int cvs_pipeline_batch(cvs_handle h, const cvs_plane* images, int n, const cvs_plane* outs)
 {
     if (!h || !images || n < 1) return CVS_E_BADARG;
     if (h->kind != CVS_KIND_G2 && !h->g4_ext) return fail(h, CVS_E_UNSUPPORTED, "the caller pipeline exists for G2, and for G4 with CVS_OPT_G4_EXTENSIONS");
     int rc;
     const int rows = images[0].rows, cols = images[0].cols;
-    bool all_dev = true;
-    size_t max_bytes = 0;
+    bool any_u8 = false;
     for (int i = 0; i < n; ++i) {
         if ((rc = check_plane(h, &images[i], "image", true)) || (rc = check_same(h, &images[i], rows, cols))) return rc;
-        all_dev = all_dev && images[i].mem == CVS_MEM_DEVICE;  // f32 on the device; 8-bit / host frames go frame by frame
-        if (!is_u8(&images[i])) max_bytes = std::max(max_bytes, (size_t)rows * images[i].step);
         for (int k = 0; outs && k < 8; ++k) {
             const cvs_plane* o = &outs[(size_t)i * 8 + k];
             if (!o->data) continue;
-            if ((rc = check_plane(h, o, "out")) || (rc = check_same(h, o, rows, cols))) return rc;
-            all_dev = all_dev && o->mem == CVS_MEM_DEVICE;
-            max_bytes = std::max(max_bytes, (size_t)rows * o->step);
+            if ((rc = check_plane(h, o, "out", true)) || (rc = check_same(h, o, rows, cols))) return rc;
+            if (outs[k].data && is_u8(o) != is_u8(&outs[k])) return fail(h, CVS_E_BADARG, "an output has another depth than in frame 0");
+            any_u8 = any_u8 || is_u8(o);
         }
         if (outs) {
             const cvs_plane* po[8];
@@ -826,7 +861,53 @@ int cvs_pipeline_batch(cvs_handle h, const cvs_plane* images, int n, const cvs_p
             if ((rc = check_no_overlap(h, &images[i], po, 8))) return rc;
         }
     }
+    h->last.u8_out = 0;
+    if (any_u8) return pipeline_u8(h, images, n, outs, true);
+    return batch_run(h, images, n, outs, nullptr);
+}
+
+// cvs_pipeline_batch with checked arguments.  u8 (the three-maps launch with 8-bit outputs, G2): mode 1 = `outs` holds the caller's byte
+// planes, mode 2 = f32 scratch planes; kNotFused = the call would not be ONE such launch, nothing was launched.
+static int batch_run(cvs_handle h, const cvs_plane* images, int n, const cvs_plane* outs, const U8Req* u8)
+{
+    int rc;
+    const int rows = images[0].rows, cols = images[0].cols;
+    bool all_dev = true;
+    size_t max_bytes = 0;
+    for (int i = 0; i < n; ++i) {
+        all_dev = all_dev && images[i].mem == CVS_MEM_DEVICE;  // f32 on the device; 8-bit / host frames go frame by frame
+        if (!is_u8(&images[i])) max_bytes = std::max(max_bytes, (size_t)rows * images[i].step);
+        for (int k = 0; outs && k < 8; ++k) {
+            const cvs_plane* o = &outs[(size_t)i * 8 + k];
+            if (!o->data) continue;
+            all_dev = all_dev && mem_of(o) == CVS_MEM_DEVICE;
+            max_bytes = std::max(max_bytes, (size_t)rows * o->step);
+        }
+    }
     if (h->kind == CVS_KIND_G4) return g4_pipeline_frames(h, images, n, outs, all_dev);
+    // gain mode: the byte planes of the three maps as ONE resource per frame -- frame 0's planes within 2 GiB of the lowest, a common
+    // row step, every frame at one constant byte stride; the f32 bookkeeping below then sees no outputs
+    const uint8_t* u8_lo = nullptr;
+    size_t u8_span = 0, u8_fstride = 0, u8_step = 0;
+    unsigned u8_off[8] = {};
+    if (u8 && u8->mode == 1) {
+        auto addr = [&](int i, int k) { return reinterpret_cast<const uint8_t*>(outs[(size_t)i * 8 + k].data); };
+        for (int k = 5; k < 8; ++k)
+            if (!u8_lo || addr(0, k) < u8_lo) u8_lo = addr(0, k);
+        bool ok = true;
+        for (int k = 5; k < 8; ++k) {
+            ok = ok && outs[k].step == outs[5].step;
+            u8_off[k] = (unsigned)std::min<size_t>((size_t)(addr(0, k) - u8_lo), 0xffffffffu);
+            u8_span = std::max(u8_span, (size_t)(addr(0, k) - u8_lo) + (size_t)rows * outs[5].step);
+        }
+        u8_fstride = n > 1 ? (size_t)(addr(1, 5) - addr(0, 5)) : 0;
+        for (int i = 1; i < n && ok; ++i)
+            for (int k = 5; k < 8 && ok; ++k)
+                ok = addr(i, k) > addr(0, k) && (size_t)(addr(i, k) - addr(0, k)) == u8_fstride * i && outs[(size_t)i * 8 + k].step == outs[5].step;
+        if (!ok || u8_span > (size_t)0x7ffffff0) return kNotFused;
+        u8_step = outs[5].step;
+        outs = nullptr;
+    }
     // 8-bit frames that lie back to back on the device (a driver's upload of a block of byte images): the one-launch path
     // below reads the bytes itself (BasisArgs::in_u8), like any regular f32 batch -- no widened copy
     bool u8_batch = n >= 1 && images[0].mem == (CVS_MEM_DEVICE | CVS_DEPTH_U8);
@@ -848,6 +929,7 @@ int cvs_pipeline_batch(cvs_handle h, const cvs_plane* images, int n, const cvs_p
     const bool small_planes = std::max(max_bytes, (size_t)rows * pitch * sizeof(float)) <= (size_t)0x7ffffff0;
     const bool fast = all_dev && small_planes &&
                       !basis_may_need_scratch(h->kind, h->width, h->taps, rows, cols, std::max(pitch, max_bytes / sizeof(float) / rows));
+    if (!fast && u8) return kNotFused;
     if (!fast) {
         // host planes, tiny or huge images, non-default taps: frame by frame through the single-image path
         for (int i = 0; i < n; ++i) {
@@ -892,6 +974,7 @@ int cvs_pipeline_batch(cvs_handle h, const cvs_plane* images, int n, const cvs_p
             }
         }
     }
+    if (!regular && u8) return kNotFused;
     if (!regular) {
         if (n > h->frame_tab_cap) {
             if (h->frame_tab) {
@@ -968,6 +1051,22 @@ int cvs_pipeline_batch(cvs_handle h, const cvs_plane* images, int n, const cvs_p
     // BasisArgs::warm_k, per frame).  32 x 1080p, same handle, alternating, sustained: +1.2 ... +2.3 % in 7 of 7 processes on three boxes
     // (four bands +1.3 %, eight +0.3 %; profiles/r06_c4_warm.txt).  Not for the outputs-only batches (-1 %: they are bound by the SIMDs).
     if (!a.no_state && regular && (size_t)rows * cols >= ((size_t)1 << 20)) a.warm_k = env_opts().warm >= 0 ? env_opts().warm : 2;
+    if (u8) {
+        if (u8->mode == 1) {   // the byte planes (out_pitch / out_off / out_bytes in bytes, out_base + z out_frame_stride a byte address)
+            a.out_one = 1;
+            a.out_mask = 0xE0u;
+            a.out_base = reinterpret_cast<float*>(const_cast<uint8_t*>(u8_lo));
+            a.out_pitch = u8_step;
+            a.out_bytes = u8_span;
+            a.out_frame_stride = u8_fstride;
+            for (int k = 0; k < 8; ++k) a.out_off[k] = u8_off[k];
+        }
+        a.u8_mode = u8->mode;
+        a.u8_gain = u8->gain;
+        a.u8_mm = u8->mm;
+        if (!basis_u8_fusable(h->kind, h->width, h->taps, a)) return kNotFused;
+        if (u8->mode == 2) HIP_TRY(h, launch_minmax_init_n(u8->mm, 3 * n, h->stream));
+    }
     TuneToken tok;
     if ((rc = tune_begin(h, a, 16 | 1 | 4 | (a.no_state ? 8 : 0), false, tok))) return rc;
     note_launch(h, a);
@@ -975,6 +1074,21 @@ int cvs_pipeline_batch(cvs_handle h, const cvs_plane* images, int n, const cvs_p
     tune_end(h, tok);
     HIP_TRY(h, le);
     h->have_basis = h->have_orient = h->persist != 0;
+    return CVS_OK;
+}
+
+int cvs_set_u8_gain(cvs_handle h, float gain)
+{
+    if (!h) return CVS_E_BADARG;
+    if (!(gain >= 0.f)) return fail(h, CVS_E_BADARG, "u8 gain: 0 (normalise) or > 0 (convertTo)");   // (NaN fails the test as well)
+    h->u8_gain = gain;
+    return CVS_OK;
+}
+
+int cvs_get_u8_gain(cvs_handle h, float* gain)
+{
+    if (!h || !gain) return CVS_E_BADARG;
+    *gain = h->u8_gain;
     return CVS_OK;
 }
 
@@ -1123,6 +1237,218 @@ int cvs_normalize_u8(cvs_handle h, const cvs_plane* src, uint8_t* dst, size_t ds
 int cvs_convert_u8(cvs_handle h, const cvs_plane* src, float alpha, float beta, uint8_t* dst, size_t dst_step, int dst_mem)
 {
     return to_u8(h, src, dst, dst_step, dst_mem, false, alpha, beta);
+}
+
+// The handle's scratch for the 8-bit pipeline outputs: `slots` min / max pairs, then `planes` f32 planes of rows x pitch (grown only;
+// the state block is never used for this: it may be parked in the process-wide cache)
+static int u8_scratch(cvs_handle h, int slots, size_t planes, int rows, size_t pitch, int** mm, float** scr)
+{
+    const size_t head = round_up((size_t)2 * slots, 64), need = head + planes * rows * pitch;
+    if (need > h->u8_scr_elems) {
+        if (h->u8_scr) {
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+            HIP_TRY(h, hipFree(h->u8_scr));
+            h->u8_scr = nullptr;
+            h->u8_scr_elems = 0;
+        }
+        HIP_TRY(h, hipMalloc(&h->u8_scr, need * sizeof(float)));
+        h->u8_scr_elems = need;
+    }
+    *mm = reinterpret_cast<int*>(h->u8_scr);
+    *scr = h->u8_scr + head;
+    return CVS_OK;
+}
+
+// Normalise mode, after the launch: plane i of the m f32 scratch planes (constant stride) into dst[i] with min / max pair i -- one
+// quantise launch when the destinations lie at one constant stride with one step, else one per plane
+static int quantize_planes(cvs_handle h, const float* scr, size_t plane_stride, size_t pitch, int rows, int cols, int m, const int* mm,
+                           const cvs_plane* const* dst)
+{
+    bool reg = true;
+    const ptrdiff_t ds = m > 1 ? reinterpret_cast<const uint8_t*>(dst[1]->data) - reinterpret_cast<const uint8_t*>(dst[0]->data) : 0;
+    for (int i = 1; i < m && reg; ++i)
+        reg = dst[i]->step == dst[0]->step && reinterpret_cast<const uint8_t*>(dst[i]->data) - reinterpret_cast<const uint8_t*>(dst[0]->data) == ds * i;
+    if (reg && ds >= 0) {
+        HIP_TRY(h, launch_quantize_n(scr, plane_stride, pitch, rows, cols, m, mm, reinterpret_cast<uint8_t*>(dst[0]->data), (size_t)ds, dst[0]->step, h->stream));
+        return CVS_OK;
+    }
+    for (int i = 0; i < m; ++i)
+        HIP_TRY(h, launch_quantize_n(scr + (size_t)i * plane_stride, plane_stride, pitch, rows, cols, 1, mm + 2 * i, reinterpret_cast<uint8_t*>(dst[i]->data), 0,
+                                     dst[i]->step, h->stream));
+    return CVS_OK;
+}
+
+// Three maps as bytes in the filter launch (G2, no state, find on magnitude, the compatible arctangent, device planes): kNotFused when
+// the launch would not be one three-maps instance
+static int pipeline_u8_fused(cvs_handle h, const cvs_plane* images, int n, const cvs_plane* outs, bool batch)
+{
+    const int rows = images[0].rows, cols = images[0].cols;
+    const bool gain = h->u8_gain > 0.f;
+    int rc;
+    if (gain) {   // the caller's byte planes straight from the epilogue
+        const U8Req rq{1, h->u8_gain, nullptr};
+        if (batch) rc = batch_run(h, images, n, outs, &rq);
+        else {
+            const cvs_plane* po[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, &outs[5], &outs[6], &outs[7]};
+            rc = do_setup(h, images, CVS_SETUP_FULL, false, 0.f, nullptr, nullptr, po, 1, 0, 0, 0, nullptr, &rq);
+        }
+        if (rc == CVS_OK) h->last.u8_out = 1;
+        return rc;
+    }
+    // normalise: f32 maps into the handle's scratch ([n][3][rows][pitch]) with min / max reduced in the same launch, then ONE quantise launch
+    const size_t pitch = round_up((size_t)cols, 64), pstride = pitch * rows;
+    int* mm = nullptr;
+    float* scr = nullptr;
+    if ((rc = u8_scratch(h, 3 * n, (size_t)3 * n, rows, pitch, &mm, &scr))) return rc;
+    std::vector<cvs_plane> so((size_t)n * 8, cvs_plane{nullptr, 0, 0, 0, 0});
+    std::vector<const cvs_plane*> dst((size_t)3 * n);
+    for (int i = 0; i < n; ++i)
+        for (int k = 5; k < 8; ++k) {
+            so[(size_t)i * 8 + k] = cvs_plane{scr + ((size_t)i * 3 + (k - 5)) * pstride, rows, cols, pitch * sizeof(float), CVS_MEM_DEVICE};
+            dst[(size_t)i * 3 + (k - 5)] = &outs[(size_t)i * 8 + k];
+        }
+    const U8Req rq{2, 0.f, mm};
+    if (batch) rc = batch_run(h, images, n, so.data(), &rq);
+    else {
+        const cvs_plane* po[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, &so[5], &so[6], &so[7]};
+        rc = do_setup(h, images, CVS_SETUP_FULL, false, 0.f, nullptr, nullptr, po, 1, 0, 0, 0, nullptr, &rq);
+    }
+    if (rc) return rc;
+    if ((rc = quantize_planes(h, scr, pstride, pitch, rows, cols, 3 * n, mm, dst.data()))) return rc;
+    h->last.u8_out = 2;
+    return CVS_OK;
+}
+
+// Any other call with 8-bit outputs: the f32 call with scratch planes in place of the byte planes, then the quantise kernels of
+// cvs_normalize_u8 / cvs_convert_u8 (to_u8_batch) -- the same bytes, by construction.  Host byte planes come down as bytes.
+static int pipeline_u8_composed(cvs_handle h, const cvs_plane* images, int n, const cvs_plane* outs, bool batch)
+{
+    const int rows = images[0].rows, cols = images[0].cols;
+    const size_t pitch = round_up((size_t)cols, 64), pstride = pitch * rows;
+    size_t m = 0;
+    for (size_t i = 0; i < (size_t)n * 8; ++i) m += (outs[i].data && is_u8(&outs[i])) ? 1 : 0;
+    int* mm = nullptr;
+    float* scr = nullptr;
+    int rc;
+    if ((rc = u8_scratch(h, 0, m, rows, pitch, &mm, &scr))) return rc;
+    std::vector<cvs_plane> so(outs, outs + (size_t)n * 8), src;
+    std::vector<const cvs_plane*> dst;
+    for (size_t i = 0; i < (size_t)n * 8; ++i) {
+        if (!outs[i].data || !is_u8(&outs[i])) continue;
+        so[i] = cvs_plane{scr + src.size() * pstride, rows, cols, pitch * sizeof(float), CVS_MEM_DEVICE};
+        src.push_back(so[i]);
+        dst.push_back(&outs[i]);
+    }
+    if (batch) rc = cvs_pipeline_batch(h, images, n, so.data());
+    else {
+        const cvs_plane* po[8];
+        for (int k = 0; k < 8; ++k) po[k] = so[k].data ? &so[k] : nullptr;
+        rc = cvs_pipeline(h, images, po);
+    }
+    if (rc) return rc;
+    // one to_u8_batch call per (row step, memory) of the destinations -- one of them in the usual case
+    std::vector<bool> done(dst.size(), false);
+    for (size_t i = 0; i < dst.size(); ++i) {
+        if (done[i]) continue;
+        std::vector<cvs_plane> gs;
+        std::vector<uint8_t*> gd;
+        for (size_t j = i; j < dst.size(); ++j)
+            if (!done[j] && dst[j]->step == dst[i]->step && mem_of(dst[j]) == mem_of(dst[i])) {
+                gs.push_back(src[j]);
+                gd.push_back(reinterpret_cast<uint8_t*>(dst[j]->data));
+                done[j] = true;
+            }
+        const bool minmax = !(h->u8_gain > 0.f);
+        if ((rc = to_u8_batch(h, gs.data(), (int)gs.size(), gd.data(), dst[i]->step, mem_of(dst[i]), minmax, minmax ? 0.f : h->u8_gain, 0.f))) return rc;
+    }
+    h->last.u8_out = 3;
+    return CVS_OK;
+}
+
+// G4 with extensions: the pair launch of every frame, then ONE k_g4_pipeline launch over all frames that writes the three maps as bytes
+// (gain; byte planes at one constant frame stride with one row step) or as f32 scratch with their min / max reduced, followed by one
+// quantise launch (normalise).  kNotFused (before anything is launched) when the byte planes do not lie that way.
+static int g4_u8_fused(cvs_handle h, const cvs_plane* images, int n, const cvs_plane* outs)
+{
+    const int rows = images[0].rows, cols = images[0].cols;
+    const bool gain = h->u8_gain > 0.f;
+    auto addr = [&](int i, int k) { return reinterpret_cast<uint8_t*>(outs[(size_t)i * 8 + k].data); };
+    G4PipeArgs a{};
+    int* mm = nullptr;
+    float* scr = nullptr;
+    const size_t pitch = round_up((size_t)cols, 64), pstride = pitch * rows;
+    int rc;
+    if (gain) {
+        const ptrdiff_t fs = n > 1 ? addr(1, 5) - addr(0, 5) : 0;
+        for (int i = 0; i < n; ++i)
+            for (int k = 5; k < 8; ++k)
+                if (addr(i, k) - addr(0, k) != fs * i || fs < 0 || outs[(size_t)i * 8 + k].step != outs[5].step) return kNotFused;
+        for (int k = 0; k < 3; ++k) a.out[G4P_EDGES + k] = {reinterpret_cast<float*>(addr(0, 5 + k)), outs[5].step, (size_t)fs};
+        a.u8_mode = 1;
+        a.u8_gain = h->u8_gain;
+    } else {
+        if ((rc = u8_scratch(h, 3 * n, (size_t)3 * n, rows, pitch, &mm, &scr))) return rc;
+        for (int k = 0; k < 3; ++k) a.out[G4P_EDGES + k] = {scr + (size_t)k * pstride, pitch, 3 * pstride};
+        a.u8_mode = 2;
+        a.u8_mm = mm;
+    }
+    for (int i = 0; i < n; ++i)
+        if ((rc = do_setup(h, &images[i], CVS_SETUP_BASIS, false, 0.f, nullptr, nullptr, nullptr, n, i))) return rc;
+    h->cur_frame = 0;
+    a.rows = rows;
+    a.cols = cols;
+    a.frames = n;
+    a.atan_mode = h->atan_mode;
+    a.find_on_e = h->find_on;
+    for (int p = 0; p < h->nb; ++p) {
+        const PlaneRef r = state_ref(h, p);
+        a.in[p] = {r.p, r.pitch, h->frame_stride};
+    }
+    a.nt_stores = use_nt_stores(h, (size_t)rows * cols * n);
+    a.nt_loads = a.nt_stores;
+    if (mm) HIP_TRY(h, launch_minmax_init_n(mm, 3 * n, h->stream));
+    HIP_TRY(h, launch_g4_pipeline(a, h->stream));
+    h->have_basis = h->have_orient = false;   // (no state kept: CVS_OPT_PERSIST_STATE = 0)
+    if (!gain) {
+        std::vector<const cvs_plane*> dst((size_t)3 * n);
+        for (int i = 0; i < n; ++i)
+            for (int k = 0; k < 3; ++k) dst[(size_t)i * 3 + k] = &outs[(size_t)i * 8 + 5 + k];
+        if ((rc = quantize_planes(h, scr, pstride, pitch, rows, cols, 3 * n, mm, dst.data()))) return rc;
+    }
+    h->last.u8_out = gain ? 1 : 2;
+    return CVS_OK;
+}
+
+static int pipeline_u8(cvs_handle h, const cvs_plane* images, int n, const cvs_plane* outs, bool batch)
+{
+    if (h->kind == CVS_KIND_G4) {   // (extensions on: checked by the entry points)
+        bool fused = !h->persist;
+        for (int i = 0; i < n && fused; ++i) {
+            fused = mem_of(&images[i]) == CVS_MEM_DEVICE;
+            for (int k = 0; k < 8 && fused; ++k) {
+                const cvs_plane& o = outs[(size_t)i * 8 + k];
+                fused = (o.data != nullptr) == (k >= 5) && (!o.data || o.mem == (CVS_MEM_DEVICE | CVS_DEPTH_U8));
+            }
+        }
+        if (fused) {
+            const int rc = g4_u8_fused(h, images, n, outs);
+            if (rc != kNotFused) return rc;
+        }
+        return pipeline_u8_composed(h, images, n, outs, batch);
+    }
+    bool fused = h->kind == CVS_KIND_G2 && !h->persist && !h->find_on && h->atan_mode == 0;
+    for (int i = 0; i < n && fused; ++i) {
+        fused = mem_of(&images[i]) == CVS_MEM_DEVICE;
+        for (int k = 0; k < 8 && fused; ++k) {
+            const cvs_plane& o = outs[(size_t)i * 8 + k];
+            fused = (o.data != nullptr) == (k >= 5) && (!o.data || o.mem == (CVS_MEM_DEVICE | CVS_DEPTH_U8));
+        }
+    }
+    if (fused) {
+        const int rc = pipeline_u8_fused(h, images, n, outs, batch);
+        if (rc != kNotFused) return rc;
+    }
+    return pipeline_u8_composed(h, images, n, outs, batch);
 }
 
 }  // extern "C"

@@ -588,23 +588,16 @@ int host_rank(const HostRun& R, Slot& s, std::string& err, double ms[3])
         for (int i = 0; i < cn; ++i) {
             if (R.u8) im[i] = cvs_plane{reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(s.in.p) + (size_t)(c0[c] + i) * plane), rows, cols, (size_t)cols, CVS_MEM_DEVICE | CVS_DEPTH_U8};
             else im[i] = cvs_plane{s.in.p + (size_t)(c0[c] + i) * plane, rows, cols, rowb, CVS_MEM_DEVICE};
+            // 8-bit outputs: the chunk's byte planes themselves -- the pipeline launch quantises (gain) or reduces min / max for one
+            // quantise launch (normalise) behind it; no f32 maps of the chunk are staged here
             for (int j = 0; j < K; ++j)
-                ou[(size_t)i * 8 + R.sel[j]] = cvs_plane{s.out.p + ((size_t)(c0[c] + i) * K + j) * plane, rows, cols, rowb, CVS_MEM_DEVICE};
+                ou[(size_t)i * 8 + R.sel[j]] = R.out8 ? cvs_plane{reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(s.out8.p) + ((size_t)(c0[c] + i) * K + j) * plane),
+                                                                   rows, cols, (size_t)cols, CVS_MEM_DEVICE | CVS_DEPTH_U8}
+                                                      : cvs_plane{s.out.p + ((size_t)(c0[c] + i) * K + j) * plane, rows, cols, rowb, CVS_MEM_DEVICE};
         }
+        if (R.out8 && (rc = cvs_set_u8_gain(s.h, b->u8_gain)) != CVS_OK) { err = std::string("cvs_set_u8_gain: ") + cvs_last_error(s.h); break; }
         rc = cvs_pipeline_batch(s.h, im.data(), cn, ou.data());
         if (rc != CVS_OK) { err = std::string("cvs_pipeline_batch: ") + cvs_last_error(s.h); break; }
-        if (R.out8) {  // the chunk's maps -> bytes on the device (one min/max + one quantise launch, queued behind the pipeline launch)
-            const size_t m = (size_t)cn * K;
-            std::vector<cvs_plane> src(m);
-            std::vector<uint8_t*> dst(m);
-            for (size_t q = 0; q < m; ++q) {
-                src[q] = cvs_plane{s.out.p + ((size_t)c0[c] * K + q) * plane, rows, cols, rowb, CVS_MEM_DEVICE};
-                dst[q] = reinterpret_cast<uint8_t*>(s.out8.p) + ((size_t)c0[c] * K + q) * plane;
-            }
-            rc = b->u8_gain > 0.f ? cvs_convert_u8_batch(s.h, src.data(), (int)m, b->u8_gain, 0.f, dst.data(), (size_t)cols, CVS_MEM_DEVICE)
-                                  : cvs_normalize_u8_batch(s.h, src.data(), (int)m, dst.data(), (size_t)cols, CVS_MEM_DEVICE);
-            if (rc != CVS_OK) { err = std::string("cvs_*_u8_batch: ") + cvs_last_error(s.h); break; }
-        }
         e = hipEventRecord(done_ev[c], s.stream);
         if (e == hipSuccess) {
             {
@@ -667,7 +660,7 @@ int run_host(cvs_batch b, const cvs_batch_cfg* cfg, const cvs_plane* inputs, con
         shard_range(F, b->world, s.rank, &lo, &hi);
         const size_t n = (size_t)(hi - lo);
         if (n && (rc = reserve(b, s, s.in, n * plane))) return rc;
-        if (n && (rc = reserve(b, s, s.out, n * K * plane))) return rc;
+        if (n && !out8 && (rc = reserve(b, s, s.out, n * K * plane))) return rc;   // (8-bit outputs: the bytes only)
         if (n && out8 && (rc = reserve(b, s, s.out8, (n * K * plane + 3) / 4 + 64))) return rc;
     }
     HostRun R{b, cfg, inputs, outputs, {0}, K, u8, out8};

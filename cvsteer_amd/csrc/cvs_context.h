@@ -47,6 +47,12 @@ struct cvs_context {
     float* arena = nullptr;
     size_t arena_elems = 0, arena_used = 0;
     float* point_out = nullptr;
+    // 8-bit pipeline outputs (cvs_set_u8_gain): 0 = normalise every map to its own min / max, > 0 = convertTo(CV_8UC1, gain).
+    // u8_scr: the handle's scratch for the f32 maps of those calls -- the min / max slots first (int pairs), then the planes; grown
+    // only, freed by cvs_destroy, never pooled with the state block
+    float u8_gain = 0.f;
+    float* u8_scr = nullptr;
+    size_t u8_scr_elems = 0;
     const void* last_image = nullptr;    // input pointer of the previous setup (fresh-input heuristic)
     int layout = 1;   // CVS_OPT_STATE_LAYOUT: 0 = planar, 1 = row-interleaved (default), 2 = one group of twelve for full G2 setups
     int atan_mode = 0, strip_rows = 0, find_on = 0, block_order = -1, persist = 1, g4_ext = 0, autotune = 1;

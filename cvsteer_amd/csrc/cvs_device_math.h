@@ -307,4 +307,19 @@ __device__ inline void g4_steer_angle(const float b[11], float theta, float& g, 
     for (int p = 6; p < 11; p++) h = __fadd_rn(h, __fmul_rn(w[p], b[p]));
 }
 
+// cv::normalize NORM_MINMAX / Mat::convertTo to CV_8UC1 (test/test.cpp:92-94, example/steer.cpp:92-104).  Min / max are reduced as
+// integer keys -- a monotone map of the float's bits -- with atomicMin / atomicMax; the quantise is saturate_cast<uchar>(v * scale +
+// shift) with cvRound's half-to-even, the op sequence every 8-bit output of the library uses (k_to_u8_n, the strip kernel's epilogue).
+__device__ __forceinline__ int float_key(float v)
+{
+    const int b = __float_as_int(v);
+    return b >= 0 ? b : b ^ 0x7fffffff;  // monotone map float -> int
+}
+__device__ __forceinline__ float key_float(int k) { return __int_as_float(k >= 0 ? k : k ^ 0x7fffffff); }
+__device__ __forceinline__ unsigned quantize_u8(float v, float scale, float shift)
+{
+    const int q = __float2int_rn(__fadd_rn(__fmul_rn(v, scale), shift));  // cvRound: half to even
+    return (unsigned)(q < 0 ? 0 : q > 255 ? 255 : q);
+}
+
 }  // namespace cvs

@@ -104,6 +104,14 @@ struct BasisArgs {
     // API layer runs the stand-alone k_pyr_down otherwise (identical values).
     float* pyr_out;
     size_t pyr_pitch;          // elements
+    // 8-bit outputs of the three-maps launch (F_FEAT3 only; 0 = off).  1 = GAIN: the epilogue quantises edges / dark / bright with
+    // convertTo(CV_8UC1, u8_gain) and stores bytes -- pipe_out[k].pitch (single image) and out_pitch / out_off / out_bytes (regular batch)
+    // are then in BYTES, out_frame_stride and out_base are byte addresses.  2 = NORMALISE: the f32 maps go to the outputs as usual
+    // (the handle's scratch) and the launch also reduces min / max of every (frame, map) into u8_mm[2 (3 z + k) ..] (float_key slots,
+    // initialised by the caller); one quantise launch follows.
+    int u8_mode;
+    float u8_gain;
+    int* u8_mm;
 };
 
 // basis plane p of a launch, whatever group it is in
@@ -123,6 +131,8 @@ bool basis_may_need_scratch(int kind, int width, const float (*taps)[kMaxTaps], 
 // true when a.pyr_out (the next pyramid level) is written by the filter launch itself; otherwise launch_basis adds a
 // k_pyr_down launch behind it (same values either way)
 bool basis_fuses_pyr(int kind, int width, const float (*taps)[kMaxTaps], const BasisArgs& a);
+// true when launch_basis runs `a` (u8_mode != 0) as one launch of a three-maps instance with 8-bit outputs; false = the API layer composes
+bool basis_u8_fusable(int kind, int width, const float (*taps)[kMaxTaps], const BasisArgs& a);
 
 // ---- pointwise kernels ("K2..K5") ----
 enum PointOp {
@@ -175,6 +185,12 @@ struct G4PipeArgs {
     int atan_mode;
     int find_on_e;            // 1 = find*(e, phase), 0 = find*(magnitude, phase)
     int nt_stores, nt_loads;
+    // 8-bit edges / dark / bright (outputs G4P_EDGES..G4P_BRIGHT; 0 = off): 1 = GAIN, those three planes are bytes (pitch and
+    // frame_stride in BYTES) written as convertTo(CV_8UC1, u8_gain); 2 = NORMALISE, they are f32 and the launch also reduces their min /
+    // max per frame into u8_mm[2 (3 z + k) ..] (float_key slots, initialised by the caller)
+    int u8_mode;
+    float u8_gain;
+    int* u8_mm;
 };
 hipError_t launch_g4_pipeline(const G4PipeArgs& a, hipStream_t s);
 // single-pixel steer (G2.cpp:115-134): uses a.w, a.c2t, a.s2t; writes {g2,h2,e,mag,phase} to out5 (device)
@@ -183,6 +199,10 @@ hipError_t launch_steer_point(const float* basis, size_t plane_stride, size_t of
 
 // per-image min/max + 8-bit quantise (cv::normalize NORM_MINMAX -> CV_8UC1)
 hipError_t launch_minmax(const float* src, size_t pitch, int rows, int cols, float* minmax2, hipStream_t s);
+// 8-bit pipeline outputs: n min / max slot pairs set to the empty range; then plane i of n normalised with pair i (k_to_u8_n)
+hipError_t launch_minmax_init_n(int* mm, int n, hipStream_t s);
+hipError_t launch_quantize_n(const float* src, size_t plane_stride, size_t pitch, int rows, int cols, int n, const int* mm, uint8_t* dst,
+                             size_t dst_plane_stride, size_t dst_step, hipStream_t s);
 // n equally sized planes at a constant stride, one launch: min / max per plane (minmax = true, minmax2n = 2n floats of
 // scratch) or convertTo(alpha, beta), 8-bit results at dst + z * dst_plane_stride
 hipError_t launch_to_u8_n(const float* src, size_t plane_stride, size_t pitch, int rows, int cols, int n, bool minmax, float* minmax2n,

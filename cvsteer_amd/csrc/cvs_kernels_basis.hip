@@ -255,12 +255,13 @@ __device__ __forceinline__ f2 pk_fma(f2 t, f2 x, f2 acc)
     return acc;
 }
 
-enum { F_ORIENT = 1, F_STEER = 2, F_PIPE = 4, F_NOSTATE = 8, F_PYR = 16, F_PYRONLY = 32, F_FEAT3 = 64 };  // F_PIPE implies F_ORIENT; F_NOSTATE: outputs only;
+enum { F_ORIENT = 1, F_STEER = 2, F_PIPE = 4, F_NOSTATE = 8, F_PYR = 16, F_PYRONLY = 32, F_FEAT3 = 64, F_U8G = 128, F_U8N = 256 };  // F_PIPE implies F_ORIENT; F_NOSTATE: outputs only;
                                                                             // F_FEAT3 (with F_NOSTATE): exactly the three feature maps, find*(magnitude, phase), fastAtan2 --
                                                                             // what example/steer.cpp keeps -- decided at COMPILE time: no per-output tests and branches in the row
                                                                             // loop, no second arctangent path in the instruction cache (+3.5 % on 32 x 1080p; same values);
                                                                             // F_PYR: also emit cv::pyrDown(image) (next pyramid level);
-                                                                            // F_PYRONLY (with F_PYR): nothing but that -- cvs_pyr_down as a strip march
+                                                                            // F_PYRONLY (with F_PYR): nothing but that -- cvs_pyr_down as a strip march;
+                                                                            // F_U8G / F_U8N (with F_FEAT3): the three maps as bytes, BasisArgs::u8_mode 1 / 2
 
 // Addressing idiom: buffer instructions.  A plane is a raw buffer resource (4 SGPRs, built from
 // wave-uniform values only), the row is the scalar offset (one SGPR, `soffset`), the lane's column
@@ -295,6 +296,12 @@ template <bool STREAM>
 __device__ __forceinline__ void bst(rsrc_t r, unsigned lane_off, unsigned row_off, float v)
 {
     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, lane_off, row_off, STREAM ? kStreamAux : 0);
+}
+// one byte per lane (8-bit outputs, F_U8G): lane_off is the pixel index, or kLaneOff
+template <bool STREAM>
+__device__ __forceinline__ void bst8(rsrc_t r, unsigned lane_off, unsigned row_off, unsigned v)
+{
+    __builtin_amdgcn_raw_buffer_store_b8((unsigned char)v, r, lane_off, row_off, STREAM ? kStreamAux : 0);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -500,8 +507,10 @@ __device__ __forceinline__ bool pick_tile(const BasisArgs& a, int* s_tile, int& 
 // 7 % on fresh images (profiles/r03_wpb_probe.txt): the four strips of a workgroup write 1 KiB of every plane row from one CU.
 #ifdef CVS_DIAG_CANARY
 #define CVS_BST(ST, ...) (++st_tally, bst<ST>(__VA_ARGS__))
+#define CVS_BST8(ST, ...) (++st_tally, bst8<ST>(__VA_ARGS__))
 #else
 #define CVS_BST(ST, ...) bst<ST>(__VA_ARGS__)
+#define CVS_BST8(ST, ...) bst8<ST>(__VA_ARGS__)
 #endif
 // Fused scalar steer (G2.cpp:137-145 / G4.cpp:114-122) of one output row: g and / or h from the bank's planes b and the host-computed weights,
 // stored to the caller's two planes -- whose pointer and pitch are read from the kernel arguments per row (kernarg_fresh: kept in scalar
@@ -539,8 +548,10 @@ __device__ __forceinline__ void store_steered(const BasisArgs& a, const float (&
 // v_readlane_b32 costs the SIMD as much as a packed multiply-add (180 of them per output row were 38 % of this variant's vector time).  They are
 // read from the kernel-argument segment again in every row instead (scalar cache); the record count of the resource is the constant maximum
 // -- the range check is only there to drop the lanes right of the image.
-template <bool STREAM, bool FEAT3, bool FROM_KERNARG>
-__device__ __forceinline__ void store_pipe_planes(const PlaneRef (&pipe_out)[8], const float (&q)[8], const unsigned xbr, const unsigned yo, [[maybe_unused]] unsigned& st_tally)
+// U8G: the three maps as bytes, convertTo(CV_8UC1, gain) -- pitch in bytes, lane offset xb8 = the pixel index.
+template <bool STREAM, bool FEAT3, bool FROM_KERNARG, bool U8G = false>
+__device__ __forceinline__ void store_pipe_planes(const PlaneRef (&pipe_out)[8], const float (&q)[8], const unsigned xbr, const unsigned yo, [[maybe_unused]] unsigned& st_tally,
+                                                  [[maybe_unused]] const unsigned xb8 = 0, [[maybe_unused]] const float gain = 0.f)
 {
 #pragma unroll
     for (int k = FEAT3 ? 5 : 0; k < 8; ++k) {
@@ -550,7 +561,8 @@ __device__ __forceinline__ void store_pipe_planes(const PlaneRef (&pipe_out)[8],
             po.p = ka->pipe_out[k].p;
             po.pitch = ka->pipe_out[k].pitch;
         }
-        if (FEAT3 || po.p) CVS_BST(STREAM, plane_rsrc(po.p, kMaxPlaneBytes), xbr, yo * (unsigned)(po.pitch * sizeof(float)), q[k]);
+        if constexpr (U8G) CVS_BST8(STREAM, plane_rsrc(po.p, kMaxPlaneBytes), xb8, yo * (unsigned)po.pitch, quantize_u8(q[k], gain, 0.f));
+        else if (FEAT3 || po.p) CVS_BST(STREAM, plane_rsrc(po.p, kMaxPlaneBytes), xbr, yo * (unsigned)(po.pitch * sizeof(float)), q[k]);
     }
 }
 
@@ -670,8 +682,11 @@ __device__ __forceinline__ float pyr_column(const float (&hw)[5])
 }
 
 template <class B, int FLAGS, bool STREAM, int BATCH, bool ONE, int WPB, bool U8 = false, bool LIT = false>
-__device__ __forceinline__ void basis_body(const BasisArgs& a, const Folded<B>& t, float* line, int zframe, const int bx, const int by)
+__device__ __forceinline__ void basis_body(const BasisArgs& a, const Folded<B>& t, float* line, int zframe, const int bx, const int by,
+                                           [[maybe_unused]] float (&mm)[6])
 {
+    constexpr bool U8G = (FLAGS & F_U8G) != 0, U8N = (FLAGS & F_U8N) != 0;
+    static_assert(!(U8G || U8N) || (FLAGS & F_FEAT3) != 0, "8-bit outputs exist for the three-maps launch only");
     constexpr unsigned EB = U8 ? 1u : 4u;   // bytes per input sample
     constexpr int W = B::W, NT = 2 * W + 1, NB = B::NB;
     // packed arithmetic everywhere but in the pipeline variants (F_PIPE): a packed instruction takes the whole SIMD, a plain one with a scalar tap
@@ -706,6 +721,7 @@ __device__ __forceinline__ void basis_body(const BasisArgs& a, const Folded<B>& 
     const bool xin = x < a.cols;
     // per-lane byte offsets, fixed for the whole strip; kLaneOff = "this lane does not take part" (hardware range check)
     const unsigned xb = xin ? (unsigned)x * 4u : kLaneOff;
+    [[maybe_unused]] const unsigned xb8 = xin ? (unsigned)x : kLaneOff;   // F_U8G: byte planes
     // input columns (REFLECT_101, bytes of the image's own type): lane l fetches column x0 - W + l into word l of the line, lanes
     // < 2W also column x0 - W + 64 + l into word 64 + l.  Columns beyond cols + W feed no valid output; they are clamped into the row.
     const unsigned dmb = (unsigned)max(0, min(reflect1(x0 - W + lane, a.cols), a.cols - 1)) * EB;
@@ -722,7 +738,8 @@ __device__ __forceinline__ void basis_body(const BasisArgs& a, const Folded<B>& 
         basis_p += (size_t)zframe * a.frame_stride;
         orient_p += (size_t)zframe * a.frame_stride;
         in_p = reinterpret_cast<const float*>(reinterpret_cast<const char*>(in_p) + (size_t)zframe * a.in_frame_stride * EB);
-        r_out = plane_rsrc(a.out_base + (size_t)zframe * a.out_frame_stride, a.out_bytes);
+        if constexpr (U8G) r_out = plane_rsrc(reinterpret_cast<float*>(reinterpret_cast<char*>(a.out_base) + (size_t)zframe * a.out_frame_stride), a.out_bytes);
+        else r_out = plane_rsrc(a.out_base + (size_t)zframe * a.out_frame_stride, a.out_bytes);
     } else if constexpr (BATCH == 1) {
         basis_p += (size_t)zframe * a.frame_stride;
         orient_p += (size_t)zframe * a.frame_stride;
@@ -973,7 +990,7 @@ __device__ __forceinline__ void basis_body(const BasisArgs& a, const Folded<B>& 
                 [[maybe_unused]] unsigned b2_pitch_b = 0, b2_mask = 0, b2_off[8] = {};
                 if constexpr (BATCH == 2 && (FLAGS & F_NOSTATE) != 0 && (FLAGS & F_PIPE) != 0) {
                     const kernarg_ptr_t ka = kernarg_fresh();
-                    b2_pitch_b = (unsigned)(ka->out_pitch * sizeof(float));
+                    b2_pitch_b = (unsigned)(U8G ? ka->out_pitch : ka->out_pitch * sizeof(float));
                     b2_mask = (FLAGS & F_FEAT3) != 0 ? 0xE0u : ka->out_mask;
 #pragma unroll
                     for (int k = (FLAGS & F_FEAT3) != 0 ? 5 : 0; k < 8; ++k) b2_off[k] = ka->out_off[k];
@@ -1027,13 +1044,22 @@ __device__ __forceinline__ void basis_body(const BasisArgs& a, const Folded<B>& 
                     if constexpr ((FLAGS & F_PIPE) != 0) {
                         float q[8];
                         pipe_values<FEAT3>(b, th, c1, c2, c3, need_e, amode, !FEAT3 && a.find_on_e, q);
+                        if constexpr (U8N) {   // cv::normalize's min / max of the three maps: fminf / fmaxf skip NaNs as k_minmax_n does
+#pragma unroll
+                            for (int k = 0; k < 3; ++k) {
+                                mm[k] = fminf(mm[k], q[5 + k]);
+                                mm[3 + k] = fmaxf(mm[3 + k], q[5 + k]);
+                            }
+                        }
                         if constexpr (BATCH == 2) {
                             if constexpr ((FLAGS & F_NOSTATE) != 0) {   // outputs only: pitch and plane offsets were read at the top of this row's block (not kept across
                                                                         // rows; with the state planes written too that costs more scalar work than it saves)
                                 const unsigned orow_out = yo * b2_pitch_b;
 #pragma unroll
-                                for (int k = FEAT3 ? 5 : 0; k < 8; ++k)
-                                    if (FEAT3 || (b2_mask & (1u << k))) CVS_BST(STREAM, r_out, xbr, orow_out + b2_off[k], q[k]);
+                                for (int k = FEAT3 ? 5 : 0; k < 8; ++k) {
+                                    if constexpr (U8G) CVS_BST8(STREAM, r_out, xb8, orow_out + b2_off[k], quantize_u8(q[k], a.u8_gain, 0.f));
+                                    else if (FEAT3 || (b2_mask & (1u << k))) CVS_BST(STREAM, r_out, xbr, orow_out + b2_off[k], q[k]);
+                                }
                             } else {
                                 const unsigned orow_out = yo * (unsigned)(a.out_pitch * sizeof(float));
 #pragma unroll
@@ -1041,7 +1067,7 @@ __device__ __forceinline__ void basis_body(const BasisArgs& a, const Folded<B>& 
                                     if (a.out_mask & (1u << k)) CVS_BST(STREAM, r_out, xbr, orow_out + a.out_off[k], q[k]);
                             }
                         } else {
-                            store_pipe_planes<STREAM, FEAT3, BATCH == 0>(pipe_out, q, xbr, yo, st_tally);
+                            store_pipe_planes<STREAM, FEAT3, BATCH == 0, U8G>(pipe_out, q, xbr, yo, st_tally, xb8, a.u8_gain);
                         }
                     }
                 }
@@ -1064,6 +1090,15 @@ __device__ __forceinline__ void basis_body(const BasisArgs& a, const Folded<B>& 
 #pragma unroll
         for (int j = 0; j < NT; ++j) row_step(std::integral_constant<int, 1>{}, g, j, more);
     }
+    if constexpr (U8N) {   // lanes right of the image filtered clamped columns: they take no part in min / max (xin is fixed for the strip)
+        if (!xin) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                mm[k] = INFINITY;
+                mm[3 + k] = -INFINITY;
+            }
+        }
+    }
 #ifdef CVS_DIAG_CANARY
     if (cn_stale) atomicAdd(&g_canary[0], (unsigned long long)cn_stale);
     if (lane == 0) {
@@ -1075,6 +1110,41 @@ __device__ __forceinline__ void basis_body(const BasisArgs& a, const Folded<B>& 
 }
 
 #undef CVS_BST
+#undef CVS_BST8
+
+// F_U8N: the min / max of this workgroup's tile (one frame: a workgroup takes exactly one tile) -- per wave through cross-lane
+// shuffles, per workgroup through LDS, then ONE atomic pair per map on the frame's float_key slots (per-wave atomics would put
+// thousands on one cache line, what k_minmax_n avoids as well).  Every wave of the workgroup comes here, those that had no
+// columns of the image included (they hold the identities).
+template <int FLAGS, int WPB>
+__device__ __forceinline__ void u8_flush(const BasisArgs& a, float (&mm)[6], unsigned z)
+{
+    if constexpr ((FLAGS & F_U8N) != 0) {
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                mm[k] = fminf(mm[k], __shfl_xor(mm[k], off));
+                mm[3 + k] = fmaxf(mm[3 + k], __shfl_xor(mm[3 + k], off));
+            }
+        }
+        __shared__ float s_mm[WPB][6];
+        if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) s_mm[threadIdx.x >> 6][k] = mm[k];
+        }
+        __syncthreads();
+        if (threadIdx.x < 6) {
+            const int k = threadIdx.x;
+            float v = s_mm[0][k];
+#pragma unroll
+            for (int w = 1; w < WPB; ++w) v = k < 3 ? fminf(v, s_mm[w][k]) : fmaxf(v, s_mm[w][k]);
+            int* slot = a.u8_mm + 2 * (3 * (size_t)z + (k % 3));
+            if (k < 3) atomicMin(slot, float_key(v));
+            else atomicMax(slot + 1, float_key(v));
+        }
+    }
+}
 // The prologue of the single-bank strip kernels: the tile of this workgroup (pick_tile) and, in a batch, its frame z; false = none.
 // Frame batches with state kept: the frames are dispatched dealt from z_ways equal parts of the batch in turn (0, n/2, 1,
 // n/2 + 1, ... for two), so that the frames in flight together -- about ten of 1080p -- have their state planes, inputs and
@@ -1104,7 +1174,9 @@ __global__ __launch_bounds__(64 * WPB, B::MIN_WAVES) void k_basis(const BasisArg
     int bx = 0, by = 0;
     unsigned z = 0;
     if (!pick_frame_tile<BATCH>(a, &s_tile, bx, by, z)) return;
-    basis_body<B, FLAGS, STREAM, BATCH, ONE, WPB, U8>(a, t, lds[threadIdx.x >> 6], z, bx, by);
+    float mm[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    basis_body<B, FLAGS, STREAM, BATCH, ONE, WPB, U8>(a, t, lds[threadIdx.x >> 6], z, bx, by, mm);
+    u8_flush<FLAGS, WPB>(a, mm, z);
 }
 
 // The pipeline variants with the reference's default taps compiled in (TapsLitG2): single-resource form.  `t` is still passed (same
@@ -1118,7 +1190,9 @@ __global__ __launch_bounds__(256, B::MIN_WAVES) void k_basis_lit(const BasisArgs
     int bx = 0, by = 0;
     unsigned z = 0;
     if (!pick_frame_tile<BATCH>(a, &s_tile, bx, by, z)) return;
-    basis_body<B, FLAGS, STREAM, BATCH, true, 4, U8, true>(a, t, lds[threadIdx.x >> 6], z, bx, by);
+    float mm[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    basis_body<B, FLAGS, STREAM, BATCH, true, 4, U8, true>(a, t, lds[threadIdx.x >> 6], z, bx, by, mm);
+    u8_flush<FLAGS, 4>(a, mm, z);
 }
 
 // G + H half banks in ONE launch: blockIdx.z picks the half bank (a wave-uniform branch), so both halves share
@@ -1132,8 +1206,9 @@ __global__ __launch_bounds__(256) void k_basis_pair(const BasisArgs a, const Fol
     int bx = 0, by = 0;
     unsigned z = 0;
     if (!pick_tile(a, &s_tile, bx, by, z)) return;   // z = half bank (dynamic order: tiles of both halves come from one set of queues)
-    if (z == 0) basis_body<BG, FLAGS, STREAM, false, ONE, 4, U8>(a, tg, lds[threadIdx.x >> 6], 0, bx, by);
-    else basis_body<BH, FLAGS, STREAM, false, ONE, 4, U8>(a, th, lds[threadIdx.x >> 6], 0, bx, by);
+    float mm[6];   // (no 8-bit outputs here)
+    if (z == 0) basis_body<BG, FLAGS, STREAM, false, ONE, 4, U8>(a, tg, lds[threadIdx.x >> 6], 0, bx, by, mm);
+    else basis_body<BH, FLAGS, STREAM, false, ONE, 4, U8>(a, th, lds[threadIdx.x >> 6], 0, bx, by, mm);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1416,9 +1491,13 @@ static bool with_variant(const BasisArgs& a, bool banded, F&& f)
     bool feat3 = a.no_state && !a.find_on_e && a.atan_mode == 0;
     if (batch2) feat3 = feat3 && a.out_mask == 0xE0u;
     else for (int k = 0; k < 8; ++k) feat3 = feat3 && ((a.pipe_out[k].p != nullptr) == (k >= 5));
+    // 8-bit outputs (BasisArgs::u8_mode) exist in the three-maps instances only: anything else is refused, never written as floats
+    if (a.u8_mode && (!feat3 || banded || (!batch2 && (a.frames || a.batch_regular)))) return false;
     auto pipeline = [&](auto batch) {
         constexpr int BATCH = decltype(batch)::value;
         if constexpr (BATCH != 1) {
+            if (feat3 && a.u8_mode == 1) return f(Variant<F_ORIENT | F_PIPE | F_NOSTATE | F_FEAT3 | F_U8G, BATCH>{});
+            if (feat3 && a.u8_mode == 2) return f(Variant<F_ORIENT | F_PIPE | F_NOSTATE | F_FEAT3 | F_U8N, BATCH>{});
             if (feat3) return f(Variant<F_ORIENT | F_PIPE | F_NOSTATE | F_FEAT3, BATCH>{});
         }
         if (a.no_state) return f(Variant<F_ORIENT | F_PIPE | F_NOSTATE, BATCH>{});
@@ -1449,12 +1528,16 @@ static hipError_t launch_bank(BasisArgs& a, const Folded<BankG2>& f, hipStream_t
     using B = BankG2;
     const StripPlan p = plan_strips(a, &f);
     if (a.lit_used) *a.lit_used = 0;
+    // the 8-bit-output instances exist in the single-resource form only (cvs_basis_u8_fusable has checked that the launch takes it)
+    if (a.u8_mode && !p.one) return hipErrorInvalidValue;
     const bool ok = with_variant(a, p.banded, [&](auto v) {
         constexpr int FL = decltype(v)::flags, BATCH = decltype(v)::batch;
         with_bools([&](auto stream, auto one, auto u8, auto lit) {
             constexpr bool ST = decltype(stream)::value, ONE = decltype(one)::value, U8 = decltype(u8)::value;
+            if constexpr ((FL & (F_U8G | F_U8N)) != 0 && !ONE) {
+                return;   // (not instantiated; refused above)
             // k_basis_lit: the whole G2 bank's pipeline variants in the single-resource form, table batches (BATCH 1) excepted
-            if constexpr (decltype(lit)::value && ONE && (FL & F_PIPE) != 0 && BATCH != 1) {
+            } else if constexpr (decltype(lit)::value && ONE && (FL & F_PIPE) != 0 && BATCH != 1) {
                 if (a.lit_used) *a.lit_used = 1;
                 hipLaunchKernelGGL((k_basis_lit<B, FL, ST, BATCH, U8>), p.grid, p.block, p.lds, s, a, f);
             } else {
@@ -1632,9 +1715,26 @@ static hipError_t for_each_band(const BasisArgs& a_in, int width, F&& fn)
     return hipSuccess;
 }
 
+// Will launch_basis run `a` (u8_mode set, arguments otherwise complete) as ONE launch of a three-maps instance with 8-bit outputs?  The
+// G2 bank at its default width, the fast geometry, no bands (the byte planes' pitches are not element pitches), the single-resource
+// form, and the FEAT3 conditions of with_variant.  The API layer takes the composed route when not.
+bool basis_u8_fusable(int kind, int width, const float (*taps)[kMaxTaps], const BasisArgs& a)
+{
+    Folded<BankG2> f;
+    if (kind != 2 || width != BankG2::W || !fold_taps<BankG2>(taps, f)) return false;
+    if (!fast_geometry_ok(a, width) || band_rows(a, width) < a.rows || a.out_row_hi > a.out_row_lo || a.pyr_out || a.steer_g) return false;
+    if (a.state_bytes == 0 || a.state_bytes > kMaxPlaneBytes) return false;
+    if (!a.no_state || a.find_on_e || a.atan_mode != 0 || !a.orient || !a.pipe || a.frames) return false;
+    if (a.batch_regular) return a.out_one && a.out_mask == 0xE0u;
+    for (int k = 0; k < 8; ++k)
+        if ((a.pipe_out[k].p != nullptr) != (k >= 5)) return false;
+    return true;
+}
+
 hipError_t launch_basis(int kind, int width, const float (*taps)[kMaxTaps], const BasisArgs& a,
                         float* scratch, hipStream_t s)
 {
+    if (a.u8_mode && !basis_u8_fusable(kind, width, taps, a)) return hipErrorInvalidValue;   // never bytes written as floats
     if (a.frames || a.batch_regular) {  // batched launch: the API layer has already checked geometry and taps
         Folded<BankG2> f;
         if (kind != 2 || width != BankG2::W || !fold_taps<BankG2>(taps, f)) return hipErrorInvalidValue;

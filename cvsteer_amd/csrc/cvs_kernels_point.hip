@@ -240,9 +240,11 @@ hipError_t launch_point(PointOp op, const PointArgs& a, hipStream_t s)
 // Layout as k_point: float4 per lane when every plane allows it, dwords otherwise; blockIdx.z = frame.  The four pixels
 // of a lane are finished one after the other, so each one's 11 inputs are dead before the next one's outputs are made.
 // ---------------------------------------------------------------------------------------
-template <int VEC, bool NT, bool NTL>
+// U8: 0 = f32 outputs; 1 / 2 = the three maps as bytes / with their min / max reduced (G4PipeArgs::u8_mode)
+template <int VEC, bool NT, bool NTL, int U8 = 0>
 __global__ __launch_bounds__(256) void k_g4_pipeline(const G4PipeArgs a)
 {
+    [[maybe_unused]] float mm[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
     typedef float f4 __attribute__((ext_vector_type(4)));
     const int ncv = a.cols / VEC;
     const size_t z = blockIdx.z;
@@ -297,9 +299,32 @@ __global__ __launch_bounds__(256) void k_g4_pipeline(const G4PipeArgs a)
 #pragma unroll
                 for (int o = 0; o < G4P_NOUT; ++o) vout[o][k] = q[o];
             }
+            if constexpr (U8 == 2) {   // cv::normalize's min / max: fminf / fmaxf skip NaNs as k_minmax_n does
+#pragma unroll
+                for (int k = 0; k < 3; ++k)
+#pragma unroll
+                    for (int i = 0; i < VEC; ++i) {
+                        mm[k] = fminf(mm[k], vout[G4P_EDGES + k][i]);
+                        mm[3 + k] = fmaxf(mm[3 + k], vout[G4P_EDGES + k][i]);
+                    }
+            }
 #pragma unroll
             for (int o = 0; o < G4P_NOUT; ++o) {
                 if (!a.out[o].p) continue;
+                if constexpr (U8 == 1) {
+                    if (o >= G4P_EDGES) {   // bytes, convertTo(CV_8UC1, gain): one dword of four pixels, or one byte
+                        uint8_t* d8 = reinterpret_cast<uint8_t*>(a.out[o].p) + z * a.out[o].frame_stride + (size_t)row * a.out[o].pitch + (size_t)cv * VEC;
+                        if constexpr (VEC == 4) {
+                            const unsigned w = quantize_u8(vout[o][0], a.u8_gain, 0.f) | (quantize_u8(vout[o][1], a.u8_gain, 0.f) << 8) |
+                                               (quantize_u8(vout[o][2], a.u8_gain, 0.f) << 16) | (quantize_u8(vout[o][3], a.u8_gain, 0.f) << 24);
+                            if constexpr (NT) __builtin_nontemporal_store(w, reinterpret_cast<unsigned*>(d8));
+                            else *reinterpret_cast<unsigned*>(d8) = w;
+                        } else {
+                            *d8 = (uint8_t)quantize_u8(vout[o][0], a.u8_gain, 0.f);
+                        }
+                        continue;
+                    }
+                }
                 float* dst = a.out[o].p + z * a.out[o].frame_stride + (size_t)row * a.out[o].pitch + (size_t)cv * VEC;
                 if constexpr (VEC == 4) {
                     const f4 v = {vout[o][0], vout[o][1], vout[o][2], vout[o][3]};
@@ -312,6 +337,29 @@ __global__ __launch_bounds__(256) void k_g4_pipeline(const G4PipeArgs a)
             }
         }
     }
+    if constexpr (U8 == 2) {   // per wave, per workgroup through LDS, then ONE atomic pair per map and workgroup (blockIdx.z = frame)
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                mm[k] = fminf(mm[k], __shfl_xor(mm[k], off));
+                mm[3 + k] = fmaxf(mm[3 + k], __shfl_xor(mm[3 + k], off));
+            }
+        __shared__ float s_mm[4][6];
+        if ((threadIdx.x & 63) == 0)
+#pragma unroll
+            for (int k = 0; k < 6; ++k) s_mm[threadIdx.x >> 6][k] = mm[k];
+        __syncthreads();
+        if (threadIdx.x < 6) {
+            const int k = threadIdx.x;
+            float v = s_mm[0][k];
+#pragma unroll
+            for (int w = 1; w < 4; ++w) v = k < 3 ? fminf(v, s_mm[w][k]) : fmaxf(v, s_mm[w][k]);
+            int* slot = a.u8_mm + 2 * (3 * (size_t)z + (k % 3));
+            if (k < 3) atomicMin(slot, float_key(v));
+            else atomicMax(slot + 1, float_key(v));
+        }
+    }
 }
 
 hipError_t launch_g4_pipeline(const G4PipeArgs& a, hipStream_t s)
@@ -319,11 +367,13 @@ hipError_t launch_g4_pipeline(const G4PipeArgs& a, hipStream_t s)
     if (a.rows <= 0 || a.cols <= 0 || a.frames <= 0) return hipErrorInvalidValue;
     bool v4 = a.cols % 4 == 0;
     auto aligned = [&](const FramePlane& p) { return !p.p || (((uintptr_t)p.p & 15) == 0 && p.pitch % 4 == 0 && p.frame_stride % 4 == 0); };
+    // byte planes (u8_mode 1): a dword of four pixels needs 4-byte rows
+    auto aligned8 = [&](const FramePlane& p) { return !p.p || (((uintptr_t)p.p & 3) == 0 && p.pitch % 4 == 0 && p.frame_stride % 4 == 0); };
     for (const FramePlane& p : a.in) {
         if (!p.p) return hipErrorInvalidValue;
         v4 = v4 && aligned(p);
     }
-    for (const FramePlane& p : a.out) v4 = v4 && aligned(p);
+    for (int o = 0; o < G4P_NOUT; ++o) v4 = v4 && (a.u8_mode == 1 && o >= G4P_EDGES ? aligned8(a.out[o]) : aligned(a.out[o]));
     const int ncv = v4 ? a.cols / 4 : a.cols;
     int gx = (ncv + 255) / 256;
     if (gx > 64) gx = 64;
@@ -333,13 +383,22 @@ hipError_t launch_g4_pipeline(const G4PipeArgs& a, hipStream_t s)
         const int nz = a.frames - z0 < 65535 ? a.frames - z0 : 65535;
         G4PipeArgs b = a;
         for (FramePlane& p : b.in) p.p += (size_t)z0 * p.frame_stride;
-        for (FramePlane& p : b.out)
-            if (p.p) p.p += (size_t)z0 * p.frame_stride;
+        for (int o = 0; o < G4P_NOUT; ++o) {
+            FramePlane& p = b.out[o];
+            if (!p.p) continue;
+            if (a.u8_mode == 1 && o >= G4P_EDGES) p.p = reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(p.p) + (size_t)z0 * p.frame_stride);
+            else p.p += (size_t)z0 * p.frame_stride;
+        }
+        if (a.u8_mm) b.u8_mm = a.u8_mm + 6 * (size_t)z0;
         b.frames = nz;
         long gy = a.rows;
         if ((long)gx * gy * nz > kCap) gy = kCap / ((long)gx * nz) > 0 ? kCap / ((long)gx * nz) : 1;
         const dim3 grid(gx, (unsigned)gy, nz), block(256);
-        if (v4 && b.nt_stores && b.nt_loads) hipLaunchKernelGGL((k_g4_pipeline<4, true, true>), grid, block, 0, s, b);
+        if (b.u8_mode == 1 && v4) hipLaunchKernelGGL((k_g4_pipeline<4, true, false, 1>), grid, block, 0, s, b);
+        else if (b.u8_mode == 1) hipLaunchKernelGGL((k_g4_pipeline<1, false, false, 1>), grid, block, 0, s, b);
+        else if (b.u8_mode == 2 && v4) hipLaunchKernelGGL((k_g4_pipeline<4, false, false, 2>), grid, block, 0, s, b);
+        else if (b.u8_mode == 2) hipLaunchKernelGGL((k_g4_pipeline<1, false, false, 2>), grid, block, 0, s, b);
+        else if (v4 && b.nt_stores && b.nt_loads) hipLaunchKernelGGL((k_g4_pipeline<4, true, true>), grid, block, 0, s, b);
         else if (v4 && b.nt_stores) hipLaunchKernelGGL((k_g4_pipeline<4, true, false>), grid, block, 0, s, b);
         else if (v4) hipLaunchKernelGGL((k_g4_pipeline<4, false, false>), grid, block, 0, s, b);
         else if (b.nt_stores) hipLaunchKernelGGL((k_g4_pipeline<1, true, false>), grid, block, 0, s, b);
@@ -354,12 +413,7 @@ hipError_t launch_g4_pipeline(const G4PipeArgs& a, hipStream_t s)
 // cv::normalize(src, dst, 0, 255, NORM_MINMAX, CV_8UC1)  (test/test.cpp:92-94,
 // example/steer.cpp:96-98): per-image min/max, then saturate_cast<uchar>(v*scale + shift).
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ int float_key(float v)
-{
-    const int b = __float_as_int(v);
-    return b >= 0 ? b : b ^ 0x7fffffff;  // monotone map float -> int
-}
-__device__ __forceinline__ float key_float(int k) { return __int_as_float(k >= 0 ? k : k ^ 0x7fffffff); }
+// (float_key / key_float: cvs_device_math.h)
 
 __global__ void k_minmax_init(int* mm)
 {
@@ -646,6 +700,33 @@ hipError_t launch_to_u8_n(const float* src, size_t plane_stride, size_t pitch, i
                                     dst + (size_t)z0 * dst_plane_stride, dst_plane_stride, dst_step);
         else hipLaunchKernelGGL(k_to_u8_n<false>, dim3(gx, gy, nz), dim3(256), 0, s, sp, plane_stride, pitch, rows, cols, minmax ? mm + 2 * z0 : nullptr, alpha, beta,
                                 dst + (size_t)z0 * dst_plane_stride, dst_plane_stride, dst_step);
+    }
+    return hipGetLastError();
+}
+
+// the 8-bit pipeline outputs: min / max slots that a filter launch reduces into (cvs_pipeline*, BasisArgs::u8_mm) ...
+hipError_t launch_minmax_init_n(int* mm, int n, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_minmax_init_n, dim3((n + 255) / 256), dim3(256), 0, s, mm, n);
+    return hipGetLastError();
+}
+
+// ... and the one quantise launch behind it: plane i of n (constant strides) with min / max pair i of mm -- k_to_u8_n, no k_minmax_n
+hipError_t launch_quantize_n(const float* src, size_t plane_stride, size_t pitch, int rows, int cols, int n, const int* mm, uint8_t* dst,
+                             size_t dst_plane_stride, size_t dst_step, hipStream_t s)
+{
+    const bool vec = cols % 4 == 0 && pitch % 4 == 0 && plane_stride % 4 == 0 && reinterpret_cast<uintptr_t>(src) % 16 == 0 &&
+                     dst_step % 4 == 0 && dst_plane_stride % 4 == 0 && reinterpret_cast<uintptr_t>(dst) % 4 == 0;
+    const int lanes = vec ? cols / 4 : cols;
+    int gx = (lanes + 255) / 256; if (gx > 16) gx = 16;
+    int gy = rows > 256 ? 256 : rows;
+    if (n >= 8 && gy > 32) gy = 32;
+    for (int z0 = 0; z0 < n; z0 += 65535) {  // grid.z limit
+        const int nz = n - z0 < 65535 ? n - z0 : 65535;
+        const float* sp = src + (size_t)z0 * plane_stride;
+        uint8_t* dp = dst + (size_t)z0 * dst_plane_stride;
+        if (vec) hipLaunchKernelGGL(k_to_u8_n<true>, dim3(gx, gy, nz), dim3(256), 0, s, sp, plane_stride, pitch, rows, cols, mm + 2 * z0, 0.f, 0.f, dp, dst_plane_stride, dst_step);
+        else hipLaunchKernelGGL(k_to_u8_n<false>, dim3(gx, gy, nz), dim3(256), 0, s, sp, plane_stride, pitch, rows, cols, mm + 2 * z0, 0.f, 0.f, dp, dst_plane_stride, dst_step);
     }
     return hipGetLastError();
 }

@@ -68,13 +68,14 @@ def process_file(engine, path, outdir, gain, ext=".png"):
     if img.dtype != torch.uint8:
         img = img.to(torch.float32)
     img = img.to(dev)  # 8-bit images cross PCIe as bytes and are widened by the engine (CVS_DEPTH_U8)
-    # one launch; only the three feature maps leave the kernel (set_persist(False): no state planes)
-    feat = [torch.empty(tuple(img.shape), dtype=torch.float32, device=dev) for _ in range(3)]
+    # one launch; only the three feature maps leave it, as bytes (set_persist(False): no state planes): convertTo(gain) in the
+    # kernel's epilogue, or normalize(NORM_MINMAX) with min / max reduced in the launch and one quantise launch behind it
+    engine.set_u8_gain(gain if gain > 0 else 0.0)
+    feat = [torch.empty(tuple(img.shape), dtype=torch.uint8, device=dev) for _ in range(3)]
     outs = engine.pipeline(img, out=[None] * 5 + feat)
     base = os.path.splitext(os.path.basename(path))[0]
     written = []
-    for plane, suffix in zip(outs[5:], ("_edges", "_lines_dark", "_lines_bright")):
-        u8 = engine.convert_u8(plane, gain) if gain > 0 else engine.normalize_u8(plane)
+    for u8, suffix in zip(outs[5:], ("_edges", "_lines_dark", "_lines_bright")):
         if outdir:
             dst = os.path.join(outdir, base + suffix + ext)
             write_u8(dst, u8.cpu().numpy())

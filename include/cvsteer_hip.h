@@ -192,6 +192,9 @@ typedef struct cvs_launch_info {
     int32_t literal_taps;     /* last basis launch: 1 = it ran a kernel instance with the reference's default G2 / H2 taps compiled in as literal
                                  operands (the caller-pipeline variants of a handle made with width 4, spacing 0.67f: same values, cheaper
                                  instruction issue); 0 = taps from the kernel arguments (any other handle or launch) */
+    int32_t u8_out;           /* last cvs_pipeline / cvs_pipeline_batch call: how it made its 8-bit outputs.  0 = it had none; 1 = quantised in
+                                 the filter launch (gain); 2 = min / max reduced in the filter launch, then one quantise launch (normalise);
+                                 3 = composed: f32 maps into the handle's scratch, then the cvs_normalize_u8 / cvs_convert_u8 kernels */
 } cvs_launch_info;
 int cvs_get_launch_info(cvs_handle h, cvs_launch_info* out);
 /* the handle's idx-th tap vector (m_g1.. members), 2*width+1 floats */
@@ -260,6 +263,18 @@ int cvs_find(cvs_handle h, const cvs_plane* e, const cvs_plane* phase,
  * CVS_OPT_PERSIST_STATE = 0).  Two launches: the G4 pair launch of the basis planes, then one per-pixel pass over them.
  * G4 without the option: CVS_E_UNSUPPORTED. */
 int cvs_pipeline(cvs_handle h, const cvs_plane* image, const cvs_plane* const outs[8]);
+/* 8-bit outputs (cvs_pipeline, cvs_pipeline_batch): an output plane with mem = CVS_MEM_DEVICE | CVS_DEPTH_U8 or CVS_MEM_HOST |
+ * CVS_DEPTH_U8 receives bytes (`step` in bytes, >= cols) -- what the reference's callers write to their files (example/steer.cpp:92-104,
+ * test/test.cpp:92-94).  Any of the 8 outputs may be 8-bit, mixed with f32 ones; in a batch, output k has the same depth in every
+ * frame.  Every byte equals the f32 call followed, per plane, by cvs_normalize_u8 (gain 0, the default: each map of each frame
+ * normalised to its own min / max) or cvs_convert_u8(plane, gain, 0) (cvs_set_u8_gain > 0).  The state afterwards is that of the f32
+ * call.  The three-maps launch (edges, dark, bright as bytes, CVS_OPT_PERSIST_STATE = 0, find on magnitude, the compatible arctangent,
+ * G2, device planes) quantises in the filter launch (gain) or reduces min / max there and adds one quantise launch (normalise);
+ * every other call composes the f32 maps with the quantise kernels (cvs_launch_info.u8_out says which). */
+/* how cvs_pipeline / cvs_pipeline_batch make 8-bit outputs: gain 0 (default) = normalize(0, 255, NORM_MINMAX, CV_8UC1) per map
+ * (example/steer.cpp:98-104), gain > 0 = convertTo(CV_8UC1, gain) (steer.cpp:92-97); negative or NaN: CVS_E_BADARG */
+int cvs_set_u8_gain(cvs_handle h, float gain);
+int cvs_get_u8_gain(cvs_handle h, float* gain);
 
 /* The batch axis (example/steer.cpp:69-124,169: one independent pipeline per file): cvs_pipeline for
  * n images of identical size in ONE kernel launch (grid.z = frame; G4 with CVS_OPT_G4_EXTENSIONS = 1: one pair launch per

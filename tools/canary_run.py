@@ -1,15 +1,18 @@
 #!/usr/bin/env python3
-"""tools/canary_run.py <twin.so> [--quick] -- run the strip kernels of a CANARY twin of the library (make -C cvsteer_amd/csrc canary) over
+"""tools/canary_run.py <twin.so> [--quick] [--sections u8] -- run the strip kernels of a CANARY twin of the library (make -C cvsteer_amd/csrc canary) over
 every kind of launch bench.py times, at full size, plus a random mix of shapes / options, and print the twin's counters as one JSON line:
   stale      words read from a ring line that still held the pattern written before the load that refills the line was issued -- behind the
              hand-counted s_waitcnt vmcnt(N) that is supposed to cover the row.  MUST be 0 for libcvsteer_hip_canary.so and > 0 for
              libcvsteer_hip_canary_slack.so (counts 6 too high).
   short_rows output rows whose vector-memory stores were fewer than S_ROW, the compile-time lower bound the counts are built from.  MUST be 0.
   reads / rows  row reads checked / output rows tallied (proof that the checks ran).
-Started by tests/test_gpu_canary.py as a child process (the twin is chosen through CVSTEER_HIP_LIB before the package is imported)."""
+--sections u8 runs only the sections of the 8-bit-output instances (three maps as bytes: gain and normalise, one 4096^2 image and
+32 x 1080p frames, three launch orders), which the full run also ends with.
+Started by tests/test_gpu_canary.py (and tests/test_gpu_pipeline_u8.py for --sections u8) as a child process (the twin is chosen through CVSTEER_HIP_LIB before the package is imported)."""
 import ctypes as C, json, os, sys
 twin = os.path.abspath(sys.argv[1])
 quick = "--quick" in sys.argv
+only = sys.argv[sys.argv.index("--sections") + 1].split(",") if "--sections" in sys.argv else None
 os.environ["CVSTEER_HIP_LIB"] = twin
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import numpy as np
@@ -40,6 +43,41 @@ def section(name):
 
 gen = torch.Generator(device="cuda").manual_seed(11)
 reps = 2 if quick else 6
+
+
+def u8_sections():
+    """the three-maps instances with 8-bit outputs (BasisArgs::u8_mode): gain (byte stores in the epilogue) and normalise (min / max
+    reduced in the launch), single image and 32 x 1080p batch, f32 and 8-bit input, plain / dynamic-tail / XCD-column orders"""
+    img = torch.rand((4096, 4096), device="cuda", generator=gen)
+    img8 = (img * 255).to(torch.uint8)
+    o8 = [torch.empty((4096, 4096), dtype=torch.uint8, device="cuda") for _ in range(3)]
+    fr8 = torch.randint(0, 256, (32, 1080, 1920), dtype=torch.uint8, device="cuda", generator=gen)
+    fr = fr8.to(torch.float32)
+    fo = torch.empty((32, 3, 1080, 1920), dtype=torch.uint8, device="cuda")
+    for mode, gain in (("gain", 3.0), ("normalise", 0.0)):
+        for order in (L.ORDER_PLAIN, L.ORDER_DYNAMIC_TAIL, L.ORDER_XCD_COLUMNS):
+            f = cv.SteerableFiltersG2(None, 4, 0.67)
+            f.set_option(L.OPT_AUTOTUNE, 0)
+            f.set_option(L.OPT_BLOCK_ORDER, order)
+            f.set_persist(False)
+            f.set_u8_gain(gain)
+            for r in range(2):
+                f.pipeline(img if r == 0 else img8, out=[None] * 5 + o8)
+                assert f.launch_info()["u8_out"] == (1 if gain > 0 else 2)
+            section("u8_%s_4096_order%d" % (mode, order))
+            for r in range(2):
+                f.pipeline_batch(fr8 if r == 0 else fr, out=fo, outputs=(5, 6, 7))
+                assert f.launch_info()["u8_out"] == (1 if gain > 0 else 2)
+            section("u8_%s_32x1080p_order%d" % (mode, order))
+            del f
+
+
+if only == ["u8"]:
+    counters()
+    u8_sections()
+    tot = [sum(v[k] for v in report.values()) for k in range(4)]
+    print(json.dumps({"twin": os.path.basename(twin), "stale": tot[0], "short_rows": tot[1], "reads": tot[2], "rows": tot[3], "sections": report}))
+    sys.exit(0)
 n = 4096
 imgs = [torch.rand((n, n), device="cuda", generator=gen) for _ in range(3)]
 g, h = cv.alloc_planes(2, n, n, device="cuda")
@@ -167,5 +205,6 @@ for it in range(30 if quick else 120):
     del f
 os.environ.pop("CVS_OPTS", None)
 section("random_small_shapes")
+u8_sections()
 tot = [sum(v[k] for v in report.values()) for k in range(4)]
 print(json.dumps({"twin": os.path.basename(twin), "stale": tot[0], "short_rows": tot[1], "reads": tot[2], "rows": tot[3], "sections": report}))
