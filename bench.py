@@ -10,6 +10,11 @@ SteerableFiltersG2.cpp:62-68) + steer(theta=0.3) (G2.cpp:137-145), as ONE fused 
 (cvs_setup_steer).  Basis planes are persisted (7 planes) and g2/h2 written: 4 B read + 36 B
 written = 40 algorithmic bytes per pixel (SURVEY.md 8(d) "M2").
 
+A plain run (the default) does only what the headline needs: it sets the handle up (the online tuner settles on the caller's own
+calls), warms up, times the --steps region, writes --dump-outputs if asked and prints the line, whose `roofline` then holds the
+headline's own figures.  Everything else below -- M1, the secondary legs, the transport self-test, the clock and power readings,
+the live counter passes and the CPU baseline -- runs with --full only.
+
 The ONE JSON line (round 5: <= 6 KB, so that it survives the driver's 8 KB tail):
   * contract keys at the top level; `roofline` carries, as FLAT scalars (nested objects do not survive the driver's parse), the
     headline kernel's figures and the fractions of the legs that matter: m1_* (north_star's own target: the basis pass alone),
@@ -25,7 +30,7 @@ Multi-GPU: the image/batch axis shards with no data-path collective -- every ran
 is used for the barrier and the max-over-ranks reduction, for a self-test of the transport (one 1080p frame per rank through
 ncclSend/ncclRecv, bytes compared; after the headline and M1, which use no transport, and before every leg that does) and in the `C4_e2e` leg for the scatter of frames from rank 0 and the gather of results.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
         --dump-outputs DIR: after the headline's timed steps, rank 0 writes what the timed call returned in its last step,
         g and h, as DIR/g.npy and DIR/h.npy (float32, the rows _dump_rows() names: 32 MiB in all) -- the inputs are seeded,
         so that two builds can be compared output for output.
@@ -398,9 +403,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary legs (M1 stays: it is north_star's own target)")
-    ap.add_argument("--all-legs", action="store_true", help="also run the probe-only legs (8-bit inputs, untuned twin, host planes, two streams, tuner-off twins, pyramid parts)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run M1, the secondary legs, the live counter passes and the CPU baseline (a plain run "
+                         "sets up, warms up, times the --steps region, writes --dump-outputs and prints the line)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the secondary legs (M1 stays: it is north_star's own target)")
+    ap.add_argument("--all-legs", action="store_true", help="implies --full; also run the probe-only legs (8-bit inputs, untuned twin, host planes, two streams, tuner-off twins, pyramid parts)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
     ap.add_argument("--strip-rows", type=int, default=0)
     ap.add_argument("--extra-timeout", type=int, default=300, help="seconds the secondary legs may take before every rank gives up on them (0 = no watchdog)")
     ap.add_argument("--repeats", type=int, default=15, help="the --steps region is timed this many times; `value` is the median (spread reported beside it)")
@@ -411,6 +419,7 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the headline's timed steps, write the g and h its last step returned as DIR/g.npy, DIR/h.npy (float32, a fixed sample of rows)")
     args = ap.parse_args()
+    args.full = args.full or args.all_legs
     LEAD_IN_MS = max(0.0, args.lead_ms)
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
@@ -629,7 +638,7 @@ def main():
                    "backend": backend, "ranks_started_by": "bench.py" if os.environ.get("CVS_BENCH_SPAWNED") else ("launcher" if ws > 1 else "single process"),
                    "library_defaults": not args.strip_rows, "repeats": R, "lead_in_ms": LEAD_IN_MS,
                    "Mpix_s_min": round(ws * args.steps * npix / max(walls) / 1e6, 1), "Mpix_s_max": round(ws * args.steps * npix / min(walls) / 1e6, 1),
-                   "distinct_devices": distinct, "launch_config": cfg_index(f)},
+                   "distinct_devices": distinct, "launch_config": cfg_index(f), "full": args.full},
         "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(achieved / HBM_PEAK_GBS, 4), "frac_wall": round(achieved_wall / HBM_PEAK_GBS, 4),
                      "traffic": traffic, "traffic_source": traffic_source,
@@ -641,18 +650,19 @@ def main():
 
     # ---- north_star's own target: the G2+H2 7-basis separable pass ALONE (M1, 32 B/pix), same handle, same image, library
     # defaults, timed like the headline (median of the repeats, slowest rank) ----
-    def step_m1():
-        f.setup(img, flags=cv.SETUP_BASIS)
+    if args.full:
+        def step_m1():
+            f.setup(img, flags=cv.SETUP_BASIS)
 
-    settle(step_m1, f)
-    _w1, e1 = _time_steps(torch, step_m1, args.steps, args.warmup, barrier, repeats=R)
-    e1 = sorted(v / args.steps for v in max_over_ranks(*e1))
-    m1_ms = _median(e1)
-    rf.update({"m1_frac": round(BYTES_PER_PIX["M1"] * npix / (m1_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), "m1_ms": round(m1_ms, 5),
-               "m1_ms_min": round(e1[0], 5), "m1_ms_max": round(e1[-1], 5), "m1_Mpix_s": round(npix / (m1_ms * 1e-3) / 1e6, 1),
-               "m1_target": ">= 0.70 (north_star)"})
-    legs["M1_basis"] = [rf["m1_frac"], rf["m1_ms"], rf["m1_ms_min"], rf["m1_ms_max"], cfg_index(f), None]
-    settle(step, None, 4)   # back to the headline entry point
+        settle(step_m1, f)
+        _w1, e1 = _time_steps(torch, step_m1, args.steps, args.warmup, barrier, repeats=R)
+        e1 = sorted(v / args.steps for v in max_over_ranks(*e1))
+        m1_ms = _median(e1)
+        rf.update({"m1_frac": round(BYTES_PER_PIX["M1"] * npix / (m1_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), "m1_ms": round(m1_ms, 5),
+                   "m1_ms_min": round(e1[0], 5), "m1_ms_max": round(e1[-1], 5), "m1_Mpix_s": round(npix / (m1_ms * 1e-3) / 1e6, 1),
+                   "m1_target": ">= 0.70 (north_star)"})
+        legs["M1_basis"] = [rf["m1_frac"], rf["m1_ms"], rf["m1_ms_min"], rf["m1_ms_max"], cfg_index(f), None]
+        settle(step, None, 4)   # back to the headline entry point
 
     # ---- secondary legs (reported, not the headline) ----
     # Insurance for runs with several ranks: the secondary legs contain collectives (barriers, the RCCL scatter / gather
@@ -665,7 +675,7 @@ def main():
         os._exit(EXIT_WATCHDOG)   # non-zero: a hung or failed set of secondary legs must not look like a clean run
 
     timer = None
-    if not args.no_extra and args.extra_timeout > 0:
+    if args.full and not args.no_extra and args.extra_timeout > 0:
         timer = threading.Timer(args.extra_timeout, watchdog)
         timer.daemon = True
         timer.start()
@@ -1065,7 +1075,7 @@ def main():
             except Exception as ex:
                 rf["c3_band_split_error"] = ("%s: %s" % (type(ex).__name__, ex))[:120]
 
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         try:
             run_extras()
         except Exception as ex:   # a failing leg must not take the headline with it: print what exists, leave non-zero
@@ -1081,13 +1091,13 @@ def main():
     # work only).  One rank only: the counter passes use device 0.
     live_box = {}
     th_live = None
-    if rank == 0 and out.get("roofline") and not args.no_live_traffic and ws == 1:
+    if rank == 0 and args.full and out.get("roofline") and not args.no_live_traffic and ws == 1:
         torch.cuda.synchronize()
         th_live = threading.Thread(target=lambda: live_box.update(zip(("live", "why"), _live_traffic())))
         th_live.start()
 
     # the CPU baseline runs on rank 0's host cores (the other ranks wait in the final barrier)
-    if rank == 0 and not args.no_cpu:
+    if rank == 0 and args.full and not args.no_cpu:
         out["cpu_baseline"] = _cpu_baseline(THETA, args.all_legs)
     elif rank == 0:
         out["cpu_baseline"] = None

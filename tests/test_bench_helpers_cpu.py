@@ -41,6 +41,13 @@ def test_live_counter_passes_refuse_to_nest_under_a_profiler(bench, monkeypatch)
     assert got is None and "profiler" in why
 
 
+def test_full_is_an_option():
+    """everything beyond the headline sits behind --full, which --help names (argparse answers before torch is imported)"""
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "--full" in r.stdout, r.stdout
+
+
 def test_bytes_per_pixel_table_matches_the_survey(bench):
     """SURVEY.md 8(d) / DESIGN.md 3: algorithmic bytes per pixel of the timed legs"""
     b = bench.BYTES_PER_PIX

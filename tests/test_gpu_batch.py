@@ -498,7 +498,7 @@ def test_bench_starts_its_own_ranks_and_watchdog_emits_the_headline(tmp_path):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, CVS_BENCH_TEST_BACKEND="gloo")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--no-extra", "--repeats", "3"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "5", "--warmup", "2", "--no-extra", "--repeats", "3"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _json_line(r.stdout)
@@ -519,7 +519,7 @@ def test_bench_starts_its_own_ranks_and_watchdog_emits_the_headline(tmp_path):
     assert d["legs"]["M1_basis"][0] == rf["m1_frac"]
     assert rf["rccl_ranks"] == 0 and d["config"]["distinct_devices"] is False                 # rehearsal on one GPU
     assert "cpu_baseline" in d and d["cpu_baseline"]["kind"] == "port"        # rank 0 measures it for N > 1 as well
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "5", "--warmup", "2", "--no-cpu", "--extra-timeout", "1", "--repeats", "3"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "5", "--warmup", "2", "--no-cpu", "--extra-timeout", "1", "--repeats", "3"],
                        env=os.environ, capture_output=True, text=True, timeout=600)
     assert r.returncode == 3, (r.returncode, r.stderr[-2000:])
     d = _json_line(r.stdout)
@@ -554,6 +554,30 @@ def test_bench_dump_outputs_are_what_the_timed_call_returns(tmp_path):
         assert np.array_equal(got, want.cpu().numpy()[rows]), name
 
 
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """bench.py without --full: the headline and nothing else -- no M1, no secondary legs, no CPU baseline, no counter passes --
+    and the contract keys as a --full run carries them; the whole process stays well inside the 30 s a plain run may spend
+    outside its steps."""
+    import subprocess
+    import sys
+    import time
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "5", "--warmup", "2"],
+                       capture_output=True, text=True, timeout=600)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _json_line(r.stdout)
+    assert d["metric"].startswith("Mpix/s for G2+H2") and d["unit"] == "Mpix/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["steps"] == 5 and d["warmup"] == 2
+    assert d["config"]["full"] is False and d["config"]["repeats"] == 15
+    rf = d["roofline"]
+    assert rf["bound"] == "hbm" and 0 < rf["frac"] < 1.2 and rf["avg_launch_ms"] > 0
+    assert "legs" not in d and "m1_frac" not in rf and "sclk_mhz" not in rf and d["cpu_baseline"] is None and "extra_error" not in d
+    assert "traffic_read_bytes" not in rf                                   # the live counter passes did not run
+    assert wall < 30, wall
+
+
 def test_bench_two_ranks_with_the_secondary_legs_and_a_crashing_rank(tmp_path):
     """the N > 1 rehearsal WITH the secondary legs (round-2 verdict: the rehearsal passed --no-extra): both ranks on device 0,
     gloo for the collectives, every leg that does not need an RCCL communicator runs with its barriers and its
@@ -563,7 +587,7 @@ def test_bench_two_ranks_with_the_secondary_legs_and_a_crashing_rank(tmp_path):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, CVS_BENCH_TEST_BACKEND="gloo")
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--repeats", "3", "--leg-repeats", "1", "--no-cpu"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--repeats", "3", "--leg-repeats", "1", "--no-cpu"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)

@@ -6,7 +6,7 @@ out=$1; n=$2; a=$3; b=$4
 for i in $(seq 1 $n); do
   for lib in $a $b; do
     echo "== $lib round $i" >> $out
-    CVSTEER_HIP_LIB=$lib timeout -k 10 300 python3 bench.py --no-cpu --no-live-traffic --steps 20 --warmup 5 >> $out 2>> ${out%.txt}.err || exit 1
+    CVSTEER_HIP_LIB=$lib timeout -k 10 300 python3 bench.py --full --no-cpu --no-live-traffic --steps 20 --warmup 5 >> $out 2>> ${out%.txt}.err || exit 1
   done
 done
 python3 - "$out" <<'PY'

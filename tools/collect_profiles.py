@@ -14,7 +14,7 @@ def short(n):
     n = re.sub(r"\((cvs::PointArgs|cvs::BasisArgs|float const\*|float\*|float4|int\*).*", "", n)
     return n.replace("void ", "")
 
-# 1. kernel stats of `rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 50 --warmup 5 --no-cpu`
+# 1. kernel stats of `rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 50 --warmup 5 --no-cpu`
 def newest(pattern):
     """gpurun merges every call's files into gpurun_out/: keep only the most recent run's file"""
     fs = sorted(glob.glob(pattern), key=os.path.getmtime)
@@ -94,7 +94,7 @@ fetch, write = pmc("FETCH_SIZE", "pmc_%s"), pmc("WRITE_SIZE", "pmc_%s")
 cal_f, cal_w = pmc("FETCH_SIZE", "pmc_cal_%s"), pmc("WRITE_SIZE", "pmc_cal_%s")
 plane = 4096 * 4096 * 4
 summary = {
-    "method": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate runs of `python3 bench.py --steps 3 --warmup 1 --no-cpu` "
+    "method": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate runs of `python3 bench.py --full --steps 3 --warmup 1 --no-cpu` "
               "(no tracing combined); counters are KB per dispatch, averaged over dispatches of the kernel. "
               "gfx950 correction (MI355X_MICROARCH.md, HBM section): FETCH_SIZE reports exactly 1/2 of streamed read bytes -> x2; "
               "WRITE_SIZE is exact.  Both factors re-calibrated here on tools/membench kernels of KNOWN traffic in the same "
