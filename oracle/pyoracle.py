@@ -243,3 +243,90 @@ def normalize_minmax_u8(a):
     scale = 255.0 / (hi - lo) if hi > lo else 0.0
     v = np.rint(a * scale - lo * scale)
     return np.clip(v, 0, 255).astype(np.uint8)
+
+
+# ---- the 8-bit quantisation contract of every byte-writing kernel (cvs_device_math.h: float_key, quantize_u8), numpy only ----
+# min / max skip NaNs (fminf / fmaxf, identities +inf / -inf); normalise takes scale / shift in float64 and rounds them to f32 once;
+# the byte is rint(f32(f32(v * scale) + shift)) half to even -- two roundings, no FMA -- saturated to 0..255, NaN -> 0.
+U8_DBL_EPSILON = 2.2204460492503131e-16
+
+
+def u8_minmax(a):
+    """(lo, hi) as np.float32 over the plane's pixels with NaN skipped; an empty or all-NaN plane gives (+inf, -inf)"""
+    a = np.asarray(a, np.float32)
+    fin = a[~np.isnan(a)]
+    if fin.size == 0:
+        return np.float32(np.inf), np.float32(-np.inf)
+    return fin.min(), fin.max()
+
+
+def u8_scale_shift(lo, hi):
+    """normalise's (scale, shift) as np.float32: d = hi - lo, scale_d = 255 / d (0 unless d > DBL_EPSILON), both in float64"""
+    lo, hi = float(np.float32(lo)), float(np.float32(hi))
+    d = hi - lo
+    scale_d = 255.0 / d if d > U8_DBL_EPSILON else 0.0
+    with np.errstate(all="ignore"):
+        return np.float32(scale_d), np.float32(-lo * scale_d)
+
+
+def quantize_u8(a, scale, shift):
+    """the byte of every pixel: rint(f32(f32(v * scale) + shift)) half to even, saturated to 0..255; NaN -> 0"""
+    a = np.asarray(a, np.float32)
+    with np.errstate(all="ignore"):
+        x = (a * np.float32(scale)).astype(np.float32) + np.float32(shift)
+        q = np.rint(x.astype(np.float32))
+    q = np.where(np.isnan(q), 0.0, np.clip(q, 0.0, 255.0))
+    return q.astype(np.uint8)
+
+
+def convert_u8(a, alpha, beta=0.0):
+    """Mat::convertTo(CV_8UC1, alpha, beta) as the library computes it (alpha, beta rounded to f32 as the C ABI passes them)"""
+    return quantize_u8(a, np.float32(alpha), np.float32(beta))
+
+
+def normalize_u8(a):
+    """cv::normalize(NORM_MINMAX, CV_8UC1) as the library computes it: NaN-skipping min / max, float64 scale / shift, quantize_u8"""
+    scale, shift = u8_scale_shift(*u8_minmax(a))
+    return quantize_u8(a, scale, shift)
+
+
+def u8_ideal(a, alpha=None, beta=0.0):
+    """the float64 value each byte rounds: (v - lo) * 255 / (hi - lo) for normalise (alpha None), v * alpha + beta otherwise.
+    NaN where it is undefined (NaN or infinite pixels, a degenerate plane)"""
+    a = np.asarray(a, np.float32)
+    v = a.astype(np.float64)
+    with np.errstate(all="ignore"):
+        if alpha is None:
+            lo, hi = (float(x) for x in u8_minmax(a))
+            d = hi - lo
+            if not (np.isfinite(d) and d > U8_DBL_EPSILON):
+                return np.full(a.shape, np.nan)
+            ideal = (v - lo) * 255.0 / d
+        else:
+            ideal = v * float(np.float32(alpha)) + float(np.float32(beta))
+    return np.where(np.isfinite(ideal), ideal, np.nan)
+
+
+def u8_tie_band(a, ideal, scale, shift):
+    """pixels whose ideal lies within delta of a half-integer, where the f32 op sequence may round the other way.  delta bounds
+    the four f32 roundings (scale, shift, product, sum; half an ulp each): 2^-23 (|v scale| + |shift| + |x|), per pixel -- a
+    fixed constant would not do for offset planes (|lo| >> hi - lo), whose shift is large and cancels"""
+    v = np.asarray(a, np.float32).astype(np.float64)
+    with np.errstate(all="ignore"):
+        vs = np.abs(v * float(scale))
+        delta = 2.0 ** -23 * (vs + abs(float(shift)) + np.abs(ideal)) + 1e-300
+        frac = ideal - np.floor(ideal)
+        return np.isfinite(ideal) & (np.abs(frac - 0.5) <= delta)
+
+
+def u8_against_ideal(u8, a, alpha=None, beta=0.0):
+    """hold bytes against the float64 ideal: -> (off_band, in_band, band) -- pixels outside the tie band whose byte is not
+    clip(rint(ideal)), pixels inside it that differ by more than 1, and the size of the band.  Undefined pixels are skipped."""
+    a = np.asarray(a, np.float32)
+    ideal = u8_ideal(a, alpha, beta)
+    scale, shift = u8_scale_shift(*u8_minmax(a)) if alpha is None else (np.float32(alpha), np.float32(beta))
+    band = u8_tie_band(a, ideal, scale, shift)
+    defined = np.isfinite(ideal)
+    want = np.clip(np.rint(np.where(defined, ideal, 0.0)), 0, 255)
+    diff = np.abs(np.asarray(u8).astype(np.float64) - want)
+    return int((defined & ~band & (diff != 0)).sum()), int((band & (diff > 1)).sum()), int(band.sum())

@@ -307,6 +307,7 @@ def test_reference_gtest_basic_on_gpu(cv, ora, fish, golden_dir):
         for pl in (plane, fz):
             u8 = f.normalize_u8(pl)
             assert np.abs(u8.astype(np.int32) - ora.normalize_minmax_u8(pl).astype(np.int32)).max() <= 1
+            assert np.array_equal(u8, ora.normalize_u8(pl))                 # exact: the library's quantisation contract
             err = np.abs(_recode(u8).astype(np.float64) - gt).mean()
             assert err <= 1.0, (name, err)
             assert err <= 0.05, (name, err)
