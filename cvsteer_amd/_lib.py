@@ -71,6 +71,7 @@ SIGNATURES = {
     "cvs_read_state": (C.c_int, [C.c_void_p, C.c_int, _PP]),
     "cvs_steer_scalar": (C.c_int, [C.c_void_p, C.c_float, _PP, _PP, _PP, _PP, _PP]),
     "cvs_steer_map": (C.c_int, [C.c_void_p, _PP, _PP, _PP, _PP, _PP, _PP]),
+    "cvs_steer_bank": (C.c_int, [C.c_void_p, _FP, C.c_int, _PP]),
     "cvs_steer_point": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, _FP]),
     "cvs_mag_phase": (C.c_int, [C.c_void_p, _PP, _PP, _PP, _PP]),
     "cvs_wrap": (C.c_int, [C.c_void_p, _PP, _PP]),

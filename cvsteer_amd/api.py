@@ -296,6 +296,36 @@ class SteerableFilters:
         dominant orientation.  full=True adds (e, magnitude, phase) (G2 only)."""
         return self._steer(theta, full, out)
 
+    def steer_bank(self, thetas, full=False, outputs=None, out=None):
+        """steer(float theta, ...) at every angle of `thetas` (1-D) in one pass over the basis planes (cvs_steer_bank).
+        outputs: indices into (g, h, e, magnitude, phase), default (0, 1); full=True = all five (G4: CVS_OPT_G4_EXTENSIONS).
+        Returns one (K, H, W) array per requested kind, in that order, allocated as one block, or `out`: one (K, H, W) array or
+        sequence of K planes per kind.  Plane k of each equals steer(thetas[k]) bit for bit."""
+        if _is_torch(thetas):
+            thetas = thetas.detach().cpu().numpy()
+        th = np.ascontiguousarray(np.asarray(thetas, dtype=np.float32))
+        if th.ndim != 1 or th.size == 0:
+            raise ValueError("thetas must be a non-empty 1-D sequence of angles")
+        kinds = (0, 1, 2, 3, 4) if full else ((0, 1) if outputs is None else tuple(int(o) for o in outputs))
+        if not kinds or len(set(kinds)) != len(kinds) or any(o < 0 or o > 4 for o in kinds):
+            raise ValueError("outputs: distinct indices into (g, h, e, magnitude, phase)")
+        n = int(th.size)
+        if out is None:
+            blk = self._new((len(kinds), n) + tuple(self.shape))
+            out = [blk[i] for i in range(len(kinds))]
+        out = list(out)
+        if len(out) != len(kinds):
+            raise ValueError("out: one (K, H, W) array per requested kind")
+        planes = (Plane * (5 * n))()   # zeroed: data == NULL = not written
+        for o, arr in zip(kinds, out):
+            if len(arr) != n:
+                raise ValueError("out: each array holds one plane per angle")
+            for k in range(n):
+                planes[5 * k + o] = _plane(arr[k])
+        self._bind_stream(*out)
+        self._check(lib().cvs_steer_bank(self._h, th.ctypes.data_as(C.POINTER(C.c_float)), n, planes), "cvs_steer_bank")
+        return tuple(out)
+
 
     # -- adjacent component (SURVEY 8f): Gaussian pyramid, not part of the reference --
     def pyrDown(self, image):

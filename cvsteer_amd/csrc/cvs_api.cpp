@@ -697,6 +697,119 @@ int cvs_steer_map(cvs_handle h, const cvs_plane* theta, const cvs_plane* g, cons
     return steer_common(h, true, 0.f, theta, g, hq, e, mag, phase);
 }
 
+// the state planes a bank launch reads, as groups at a constant stride (BankArgs::in); false = the layout does not allow it
+static bool bank_inputs(cvs_handle h, bool e, BankArgs& a)
+{
+    const int nb = h->nb, split = nb == 7 ? 7 : 5;
+    const int first[3] = {0, split, nb}, count[3] = {split, nb - split, 3};
+    const int ng = (nb == 7 ? 1 : 2) + (e ? 1 : 0);
+    for (int g = 0; g < 3; ++g) a.in[g] = {nullptr, 0, 0};
+    for (int g = 0; g < ng; ++g) {
+        const int f = g == ng - 1 && e ? nb : first[g], m = g == ng - 1 && e ? 3 : count[g];
+        const PlaneRef p0 = state_ref(h, f);
+        const size_t stride = m > 1 ? (size_t)(state_plane(h, f + 1) - p0.p) : 0;
+        for (int j = 1; j < m; ++j) {
+            const PlaneRef pj = state_ref(h, f + j);
+            if (pj.p != p0.p + (size_t)j * stride || pj.pitch != p0.pitch) return false;
+        }
+        a.in[g] = {p0.p, p0.pitch, stride};
+    }
+    return true;
+}
+
+static void bank_angle(cvs_handle h, BankArgs& a, int t, float theta)
+{
+    host_steer_weights(h->kind, theta, a.w[t]);
+    // G2.cpp:162: float c2t(std::cos(theta * 2.0)) -- double argument, narrowed (steer_common)
+    a.c2t[t] = (float)std::cos((double)theta * 2.0);
+    a.s2t[t] = (float)std::sin((double)theta * 2.0);
+}
+
+int cvs_steer_bank(cvs_handle h, const float* thetas, int n, const cvs_plane* outs)
+{
+    if (!h) return CVS_E_BADARG;
+    if (n <= 0 || !thetas || !outs) return fail(h, CVS_E_BADARG, "n > 0 angles, thetas and outs are required");
+    int rc = need_state(h, false);
+    if (rc) return rc;
+    // kind o (g, h, e, magnitude, phase) is written when angle 0's plane has data -- and then for every angle
+    bool want[5], any = false;
+    for (int o = 0; o < 5; ++o) any |= (want[o] = outs[o].data != nullptr);
+    if (!any) return fail(h, CVS_E_BADARG, "no output requested");
+    for (int t = 0; t < n; ++t)
+        for (int o = 0; o < 5; ++o) {
+            const cvs_plane* p = &outs[5 * (size_t)t + o];
+            if ((p->data != nullptr) != want[o]) return fail(h, CVS_E_BADARG, "an output kind is requested for some angles but not for others");
+            if (want[o] && ((rc = check_plane(h, p, "plane")) || (rc = check_same(h, p, h->rows, h->cols)))) return rc;
+        }
+    if (h->kind == CVS_KIND_G4 && (want[2] || want[3] || want[4]) && !h->g4_ext)
+        return fail(h, CVS_E_UNSUPPORTED, "G4 has no energy / magnitude / phase in the reference (G4.cpp:88-90); see CVS_OPT_G4_EXTENSIONS");
+    if (want[2] && (rc = need_state(h, true))) return rc;
+    // no two written planes may share memory (the per-pixel rule; the state planes are the engine's own)
+    std::vector<const cvs_plane*> all;
+    for (int t = 0; t < n; ++t)
+        for (int o = 0; o < 5; ++o)
+            if (want[o]) all.push_back(&outs[5 * (size_t)t + o]);
+    for (size_t i = 0; i < all.size(); ++i)
+        for (size_t j = i + 1; j < all.size(); ++j)
+            if (planes_overlap(all[i], all[j])) return fail(h, CVS_E_BADARG, "two output planes overlap each other");
+
+    BankArgs a{};
+    a.rows = h->rows;
+    a.cols = h->cols;
+    a.atan_mode = h->atan_mode;
+    a.nt_stores = use_nt_stores(h, (size_t)a.rows * a.cols);
+    a.nt_loads = a.nt_stores;   // as cvs_steer_scalar: the state planes of an image that large are not cache-resident
+    if (!bank_inputs(h, want[2], a)) return fail(h, CVS_E_STATE, "state planes not at a constant stride within their group");
+
+    // one launch per kBankMax angles when every written plane is a device plane and each kind's planes lie at one pitch and a
+    // constant stride (a [K][H][W] or [H][K][W] block, what the Python side allocates)
+    bool one = true;
+    for (int o = 0; o < 5 && one; ++o) {
+        if (!want[o]) continue;
+        const cvs_plane* p0 = &outs[o];
+        const ptrdiff_t d = n > 1 ? (const char*)outs[5 + o].data - (const char*)p0->data : 0;
+        one = d >= 0 && d % (ptrdiff_t)sizeof(float) == 0;
+        for (int t = 0; t < n && one; ++t) {
+            const cvs_plane* p = &outs[5 * (size_t)t + o];
+            one = mem_of(p) == CVS_MEM_DEVICE && p->step == p0->step && (const char*)p->data == (const char*)p0->data + (ptrdiff_t)t * d;
+        }
+        a.out[o] = {p0->data, p0->step / sizeof(float), (size_t)d / sizeof(float)};
+    }
+    if (one) {
+        Call c;
+        if ((rc = begin(h, c, {}))) return rc;
+        for (int t0 = 0; t0 < n; t0 += kBankMax) {
+            BankArgs b = a;
+            b.n = std::min(kBankMax, n - t0);
+            for (int t = 0; t < b.n; ++t) bank_angle(h, b, t, thetas[t0 + t]);
+            for (int o = 0; o < 5; ++o)
+                if (b.out[o].p) b.out[o].p += (size_t)t0 * b.out[o].stride;
+            HIP_TRY(h, launch_steer_bank(h->nb, b, h->stream));
+        }
+        return finish(c);
+    }
+    // anything else -- host planes, separate allocations, mixed pitches -- angle by angle, each a launch of one angle (host
+    // planes staged and downloaded per angle, as cvs_steer_scalar does): the same values
+    for (int t = 0; t < n; ++t) {
+        const cvs_plane* p = &outs[5 * (size_t)t];
+        const cvs_plane* q[5];
+        for (int o = 0; o < 5; ++o) q[o] = want[o] ? &p[o] : nullptr;
+        Call c;
+        if ((rc = begin(h, c, {q[0], q[1], q[2], q[3], q[4]}))) return rc;
+        BankArgs b = a;
+        b.n = 1;
+        bank_angle(h, b, 0, thetas[t]);
+        for (int o = 0; o < 5; ++o) {
+            PlaneRef r;
+            if ((rc = out_ref(c, q[o], r))) return rc;
+            b.out[o] = {r.p, r.pitch, 0};
+        }
+        HIP_TRY(h, launch_steer_bank(h->nb, b, h->stream));
+        if ((rc = finish(c))) return rc;
+    }
+    return CVS_OK;
+}
+
 int cvs_steer_point(cvs_handle h, int x, int y, float theta, float out[5])
 {
     if (!h || !out) return CVS_E_BADARG;

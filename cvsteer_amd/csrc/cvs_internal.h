@@ -193,6 +193,31 @@ struct G4PipeArgs {
     int* u8_mm;
 };
 hipError_t launch_g4_pipeline(const G4PipeArgs& a, hipStream_t s);
+
+// ---- steering bank (cvs_steer_bank): scalar steering at n angles in ONE pass over the state planes ----
+// Every lane loads its pixels' basis values (and C1..C3 when e is written) once, then writes each requested plane of every angle:
+// the values of OP_G2_STEER_SCALAR / OP_G4_STEER_SCALAR at that angle, bit for bit.  Output kind o of angle k lies at
+// out[o].p + k * out[o].stride, row pitch out[o].pitch -- a [K][H][W] block or a row-interleaved [H][K][W] one alike.
+constexpr int kBankMax = 32;   // angles per launch: ~2 KiB of kernel arguments; the API layer cuts longer banks into launches of this many
+struct BankPlane {
+    float* p;             // the first plane of the sequence; nullptr = not written (outputs)
+    size_t pitch;         // elements
+    size_t stride;        // elements from one plane of the sequence to the next (outputs: angle to angle)
+};
+struct BankArgs {
+    int rows, cols;
+    int n;                        // angles of this launch, 1 .. kBankMax
+    int atan_mode;
+    int nt_stores, nt_loads;
+    // the state planes read, as three groups of planes at a constant stride (plane j of group g at in[g].p + j * in[g].stride, row
+    // pitch in[g].pitch): G2 = 7 basis | C1..C3, G4 = g4a..e | h4a..f | C1..C3.  C1..C3 are read only when e is written.  (Fourteen
+    // separate pointers and pitches held the kernel's scalar registers over the limit: SGPR spills to scratch.)
+    BankPlane in[3];
+    BankPlane out[5];             // g, h, e, magnitude, phase
+    float w[kBankMax][kMaxBasis]; // host_steer_weights of each angle
+    float c2t[kBankMax], s2t[kBankMax];   // (float)cos / sin((double)theta * 2.0) of each angle
+};
+hipError_t launch_steer_bank(int nb, const BankArgs& a, hipStream_t s);
 // single-pixel steer (G2.cpp:115-134): uses a.w, a.c2t, a.s2t; writes {g2,h2,e,mag,phase} to out5 (device)
 hipError_t launch_steer_point(const float* basis, size_t plane_stride, size_t offset, const float* orient, size_t orient_stride,
                               size_t orient_offset, const PointArgs& a, float* out5, hipStream_t s);   // orient may be nullptr

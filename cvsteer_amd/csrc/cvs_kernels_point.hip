@@ -19,6 +19,7 @@
 //   OP_G4_ORIENT        (extension, not in the reference) C1..C3 / theta / strength for G4+H4
 //   OP_G2_PIPELINE      test/test.cpp:86-90 / example/steer.cpp:87-90 in one pass
 //   k_g4_pipeline       (extension) OP_G4_ORIENT + OP_G4_STEER_MAP at theta_dom + OP_FIND for G4+H4 in one pass
+//   k_steer_bank        (extension) OP_G2_STEER_SCALAR / OP_G4_STEER_SCALAR at n angles from one read of the state planes
 #include <hip/hip_runtime.h>
 
 #include "cvs_device_math.h"
@@ -407,6 +408,126 @@ hipError_t launch_g4_pipeline(const G4PipeArgs& a, hipStream_t s)
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+// ---------------------------------------------------------------------------------------
+// Steering bank (cvs_steer_bank): steer(theta_k, g, h[, e, magnitude, phase]) for the n angles of a launch in one pass.
+// K separate OP_*_STEER_SCALAR launches read all nb basis planes (28 / 44 B/pix) once per angle to write two; here each
+// lane loads its pixels' basis values -- and C1..C3 when e is wanted -- ONCE and loops over the angles, so the bytes are
+// 4 nb (+ 12) + 4 x kinds x K per pixel.  Every value is the expression OP_G2_STEER_SCALAR / OP_G4_STEER_SCALAR computes
+// (g2_steer_weights / g4_steer_weights, the same energy sum, mag_phase) with the same host weights, so it equals a
+// cvs_steer_scalar call at that angle bit for bit.  NB = 7 (G2) or 11 (G4); VEC / NT / NTL as k_point.
+// ---------------------------------------------------------------------------------------
+template <int NB, int VEC, bool NT, bool NTL>
+__global__ __launch_bounds__(256) void k_steer_bank(const BankArgs a)
+{
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    constexpr int NIN = NB + 3;
+    const int ncv = a.cols / VEC;
+    // wave-uniform: which optional parts are requested
+    const bool need_e = a.out[2].p != nullptr;
+    const bool need_mp = a.out[3].p != nullptr || a.out[4].p != nullptr;
+    unsigned omask = 0;   // the kinds written
+#pragma unroll
+    for (int o = 0; o < 5; ++o) omask |= (a.out[o].p != nullptr) << o;
+    for (int row = blockIdx.y; row < a.rows; row += gridDim.y) {
+        for (int cv = blockIdx.x * blockDim.x + threadIdx.x; cv < ncv; cv += gridDim.x * blockDim.x) {
+            float vin[NIN][VEC];
+#pragma unroll
+            for (int i = 0; i < NIN; ++i) {
+                if (i < NB || need_e) {
+                    constexpr int kH = NB == 7 ? 7 : 5;   // first plane of the second group
+                    const int g = i < kH ? 0 : i < NB ? 1 : 2, j = i < kH ? i : i < NB ? i - kH : i - NB;
+                    const BankPlane& gp = a.in[NB == 7 && g == 2 ? 1 : g];
+                    const float* src = gp.p + (size_t)j * gp.stride + (size_t)row * gp.pitch + (size_t)cv * VEC;
+                    if constexpr (VEC == 4) {
+                        f4 v;
+                        if constexpr (NTL) v = __builtin_nontemporal_load(reinterpret_cast<const f4*>(src));
+                        else v = *reinterpret_cast<const f4*>(src);
+                        vin[i][0] = v.x; vin[i][1] = v.y; vin[i][2] = v.z; vin[i][3] = v.w;
+                    } else {
+                        vin[i][0] = *src;
+                    }
+                } else {
+#pragma unroll
+                    for (int k = 0; k < VEC; ++k) vin[i][k] = 0.f;
+                }
+            }
+            // this lane's pixel in angle 0's plane of every requested kind; each angle steps on by the kind's stride
+            float* dst[5];
+#pragma unroll
+            for (int o = 0; o < 5; ++o) dst[o] = (omask >> o & 1) ? a.out[o].p + (size_t)row * a.out[o].pitch + (size_t)cv * VEC : nullptr;
+            for (int t = 0; t < a.n; ++t) {
+                float w[NB];
+#pragma unroll
+                for (int i = 0; i < NB; ++i) w[i] = a.w[t][i];
+                const float c2t = a.c2t[t], s2t = a.s2t[t];
+                float vout[5][VEC];
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) {
+                    float b[NIN];
+#pragma unroll
+                    for (int i = 0; i < NIN; ++i) b[i] = vin[i][k];
+                    float q[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+                    if constexpr (NB == 7) g2_steer_weights(b, w, q[0], q[1]);
+                    else g4_steer_weights(b, w, q[0], q[1]);
+                    if (need_e) q[2] = __fadd_rn(__fadd_rn(b[NB], __fmul_rn(c2t, b[NB + 1])), __fmul_rn(s2t, b[NB + 2]));
+                    if (need_mp) mag_phase(q[0], q[1], a.atan_mode, q[3], q[4]);
+#pragma unroll
+                    for (int o = 0; o < 5; ++o) vout[o][k] = q[o];
+                }
+#pragma unroll
+                for (int o = 0; o < 5; ++o) {
+                    if (!(omask >> o & 1)) continue;
+                    if constexpr (VEC == 4) {
+                        const f4 v = {vout[o][0], vout[o][1], vout[o][2], vout[o][3]};
+                        if constexpr (NT) __builtin_nontemporal_store(v, reinterpret_cast<f4*>(dst[o]));
+                        else *reinterpret_cast<f4*>(dst[o]) = v;
+                    } else {
+                        if constexpr (NT) __builtin_nontemporal_store(vout[o][0], dst[o]);
+                        else *dst[o] = vout[o][0];
+                    }
+                    dst[o] += a.out[o].stride;
+                }
+            }
+        }
+    }
+}
+
+template <int NB>
+static void launch_bank_nb(const BankArgs& a, bool v4, dim3 grid, hipStream_t s)
+{
+    const dim3 block(256);
+    if (v4 && a.nt_stores && a.nt_loads) hipLaunchKernelGGL((k_steer_bank<NB, 4, true, true>), grid, block, 0, s, a);
+    else if (v4) hipLaunchKernelGGL((k_steer_bank<NB, 4, false, false>), grid, block, 0, s, a);
+    else if (a.nt_stores) hipLaunchKernelGGL((k_steer_bank<NB, 1, true, false>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((k_steer_bank<NB, 1, false, false>), grid, block, 0, s, a);
+}
+
+hipError_t launch_steer_bank(int nb, const BankArgs& a, hipStream_t s)
+{
+    if (a.rows <= 0 || a.cols <= 0 || a.n <= 0 || a.n > kBankMax || (nb != 7 && nb != 11)) return hipErrorInvalidValue;
+    const bool need_e = a.out[2].p != nullptr, need_mp = a.out[3].p != nullptr || a.out[4].p != nullptr;
+    // float4 per lane when every plane it touches allows it (vec4_ok), the angle strides included
+    bool v4 = a.cols % 4 == 0;
+    for (int g = 0; g < (nb == 7 ? 1 : 2) + (need_e ? 1 : 0); ++g) {
+        if (!a.in[g].p) return hipErrorInvalidValue;
+        v4 = v4 && ((uintptr_t)a.in[g].p & 15) == 0 && a.in[g].pitch % 4 == 0 && a.in[g].stride % 4 == 0;
+    }
+    for (const BankPlane& p : a.out)
+        if (p.p) v4 = v4 && ((uintptr_t)p.p & 15) == 0 && p.pitch % 4 == 0 && p.stride % 4 == 0;
+    const int ncv = v4 ? a.cols / 4 : a.cols;
+    int gx = (ncv + 255) / 256;
+    if (gx > 64) gx = 64;
+    int gy = a.rows;
+    // workgroups per CU before rows are strided, as launch_op: 16 for the weighted sums, 64 once magnitude / phase add an
+    // arctangent and a square root per angle and pixel
+    const int cap = 256 * (need_mp ? 64 : 16);
+    if ((long)gx * gy > cap) gy = cap / gx > 0 ? cap / gx : 1;
+    const dim3 grid(gx, gy);
+    if (nb == 7) launch_bank_nb<7>(a, v4, grid, s);
+    else launch_bank_nb<11>(a, v4, grid, s);
+    return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------

@@ -298,6 +298,38 @@ void SteerableFiltersG2::pipeline(const Mat1f& image, Mat1f& g2, Mat1f& h2, Mat1
     check(cvs_pipeline(m_handle, &pi, ptrs), "cvs_pipeline");
 }
 
+// steer(thetas[k], ...) for every angle in one cvs_steer_bank call: outs[o] (g, h, e, magnitude, phase; NULL = not wanted) resized
+// to one host plane per angle, allocated as the Mat1f& overloads allocate theirs
+namespace {
+int steer_bank_views(cvs_handle h, const std::vector<float>& thetas, std::vector<Mat1f>* const outs[5])
+{
+    int rows = 0, cols = 0;
+    int rc = cvs_shape(h, &rows, &cols);
+    if (rc != CVS_OK) return rc;
+    const size_t n = thetas.size();
+    std::vector<cvs_plane> planes(5 * n);
+    for (int o = 0; o < 5; ++o) {
+        if (!outs[o]) continue;
+        outs[o]->resize(n);
+        for (size_t k = 0; k < n; ++k) planes[5 * k + o] = out_view((*outs[o])[k], rows, cols);
+    }
+    return cvs_steer_bank(h, thetas.empty() ? 0 : thetas.data(), (int)n, planes.empty() ? 0 : planes.data());
+}
+}  // namespace
+
+void SteerableFiltersG2::steer(const std::vector<float>& thetas, std::vector<Mat1f>& g2, std::vector<Mat1f>& h2)
+{
+    std::vector<Mat1f>* const outs[5] = {&g2, &h2, 0, 0, 0};
+    check(steer_bank_views(m_handle, thetas, outs), "cvs_steer_bank");
+}
+
+void SteerableFiltersG2::steer(const std::vector<float>& thetas, std::vector<Mat1f>& g2, std::vector<Mat1f>& h2, std::vector<Mat1f>& e,
+                               std::vector<Mat1f>& magnitude, std::vector<Mat1f>& phase)
+{
+    std::vector<Mat1f>* const outs[5] = {&g2, &h2, &e, &magnitude, &phase};
+    check(steer_bank_views(m_handle, thetas, outs), "cvs_steer_bank");
+}
+
 // --------------------------------------------------------------------------- G4
 SteerableFiltersG4::SteerableFiltersG4(const Mat1f& image, int width, float spacing)
     : SteerableFilters(CVS_KIND_G4, width, spacing, 0)
@@ -350,6 +382,12 @@ void SteerableFiltersG4::steer(float theta, Mat1f& g4, Mat1f& h4)
 }
 
 // G4.cpp:88-90: empty body in the reference; outputs are left untouched
+void SteerableFiltersG4::steer(const std::vector<float>& thetas, std::vector<Mat1f>& g4, std::vector<Mat1f>& h4)
+{
+    std::vector<Mat1f>* const outs[5] = {&g4, &h4, 0, 0, 0};
+    check(steer_bank_views(m_handle, thetas, outs), "cvs_steer_bank");
+}
+
 void SteerableFiltersG4::computeMagnitudeAndPhase(const Mat1f&, const Mat1f&, Mat1f&, Mat1f&) {}
 
 void SteerableFiltersG4::getBasis(int index, Mat1f& dst) const { fetch(CVS_PLANE_BASIS0 + index, dst); }

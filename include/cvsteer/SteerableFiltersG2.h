@@ -7,6 +7,8 @@
 
 #include <cvsteer/SteerableFilters.h>
 
+#include <vector>
+
 namespace fa {
 
 class SteerableFiltersG2 : public SteerableFilters {
@@ -46,6 +48,11 @@ public:
     // the callers' whole sequence (test/test.cpp:85-90) in two kernel launches
     void pipeline(const Mat1f& image, Mat1f& g2, Mat1f& h2, Mat1f& e, Mat1f& magnitude, Mat1f& phase,
                   Mat1f& edges, Mat1f& linesDark, Mat1f& linesBright);
+    // steer(thetas[k], g2[k], h2[k][, e[k], magnitude[k], phase[k]]) for every angle from one read of the basis planes
+    // (cvs_steer_bank): the vectors are resized to thetas.size(), each plane allocated like the Mat1f& overloads'
+    void steer(const std::vector<float>& thetas, std::vector<Mat1f>& g2, std::vector<Mat1f>& h2);
+    void steer(const std::vector<float>& thetas, std::vector<Mat1f>& g2, std::vector<Mat1f>& h2, std::vector<Mat1f>& e,
+               std::vector<Mat1f>& magnitude, std::vector<Mat1f>& phase);
 
 protected:
     // the reference's protected members, same names (SteerableFiltersG2.h:62-66).  m_g1..m_h4 are the 7 tap vectors; the

@@ -8,6 +8,8 @@
 
 #include <cvsteer/SteerableFilters.h>
 
+#include <vector>
+
 namespace fa {
 
 class SteerableFiltersG4 : public SteerableFilters {
@@ -26,6 +28,8 @@ public:
 
     // addition: the reference's protected basis planes m_g4a..m_h4f (index 0..10)
     void getBasis(int index, Mat1f& dst) const;
+    // addition: steer(thetas[k], g4[k], h4[k]) for every angle from one read of the basis planes (cvs_steer_bank)
+    void steer(const std::vector<float>& thetas, std::vector<Mat1f>& g4, std::vector<Mat1f>& h4);
 
 protected:
     // the reference's protected members, same names (SteerableFiltersG4.h:50-56): 11 tap vectors; the planes m_g4a..m_h4f

@@ -238,6 +238,20 @@ int cvs_steer_scalar(cvs_handle h, float theta, const cvs_plane* g, const cvs_pl
  * callers do: test/test.cpp:86, example/steer.cpp:87). */
 int cvs_steer_map(cvs_handle h, const cvs_plane* theta, const cvs_plane* g, const cvs_plane* hq,
                   const cvs_plane* e, const cvs_plane* mag, const cvs_plane* phase);
+/* steer(float theta_k, g, h[, e, magnitude, phase]) -- SteerableFiltersG2.cpp:137-145, :157-165 / SteerableFiltersG4.cpp:114-122 --
+ * for k = 0 .. n-1 in one pass over the handle's state planes (each basis plane read once per call, not once per angle).
+ * EXTENSION beyond the reference, which steers one angle per call.  thetas: n host floats.  outs: a flat array of n*5 planes,
+ * angle-major, {g, h, e, magnitude, phase} for each angle (the convention of cvs_pipeline_batch); an entry with data == NULL is
+ * not written.  Every written plane equals, bit for bit, what cvs_steer_scalar(h, thetas[k], ...) writes on the same handle.
+ * Unlike cvs_steer_scalar, g and h are not required: any non-empty set of kinds may be asked for (e alone is G2 oriented energy
+ * at n angles from C1..C3), but the same set for every angle (CVS_E_BADARG otherwise).  f32 planes only; no two planes may share
+ * memory; every plane has the handle's image size (CVS_E_SIZE).  e needs orientation state (CVS_E_STATE); G4 e / magnitude / phase
+ * need CVS_OPT_G4_EXTENSIONS (CVS_E_UNSUPPORTED).  Addresses the frame chosen by cvs_select_frame.  Device planes where each
+ * kind's n planes share a step and lie at a constant distance from one another (a [n][rows][cols] block, or rows interleaved
+ * [rows][n][cols]) take one kernel launch per 32 angles, asynchronous on the handle's stream; any other placement (separate
+ * allocations, host planes) runs angle by angle with the same values, and returns after the data has landed when a plane is a
+ * host plane. */
+int cvs_steer_bank(cvs_handle h, const float* thetas, int n, const cvs_plane* outs);
 /* steer(const cv::Point& p, theta, g2, h2, e, magnitude, phase) G2.cpp:115-134 (p.x=col, p.y=row).
  * out = {g2, h2, e, magnitude, phase}; e is NaN when orientation state is absent. */
 int cvs_steer_point(cvs_handle h, int x, int y, float theta, float out[5]);
