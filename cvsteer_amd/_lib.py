@@ -77,6 +77,8 @@ SIGNATURES = {
     "cvs_wrap": (C.c_int, [C.c_void_p, _PP, _PP]),
     "cvs_phase_weights": (C.c_int, [C.c_void_p, _PP, _PP, C.c_float, C.c_int, C.c_float]),
     "cvs_find": (C.c_int, [C.c_void_p, _PP, _PP, _PP, _PP, _PP]),
+    "cvs_nonmax": (C.c_int, [C.c_void_p, _PP, C.c_int, _PP, _PP]),
+    "cvs_hysteresis": (C.c_int, [C.c_void_p, C.c_int, _PP, C.c_float, C.c_float, _PP, _IP]),
     "cvs_pipeline": (C.c_int, [C.c_void_p, _PP, C.POINTER(_PP)]),
     "cvs_pipeline_batch": (C.c_int, [C.c_void_p, _PP, C.c_int, _PP]),
     "cvs_set_u8_gain": (C.c_int, [C.c_void_p, C.c_float]),

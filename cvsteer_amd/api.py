@@ -489,6 +489,63 @@ class _CallerPipeline:
         self._batch_keepalive = (planes, out)
         return out
 
+    # -- contour thinning (extension beyond the reference): cvs_nonmax / cvs_hysteresis --
+    @staticmethod
+    def _plane_list(maps, most, what):
+        single = (_is_torch(maps) or isinstance(maps, np.ndarray)) and maps.ndim == 2
+        ms = [maps] if single else list(maps)
+        if not 1 <= len(ms) <= most:
+            raise ValueError("%s: one plane or a sequence of 1..%d planes" % (what, most))
+        return single, ms
+
+    def nonmax(self, maps, theta=None, out=None):
+        """Thin maps (one plane or a sequence of up to 3, e.g. edges / dark / bright) to their local maxima across the orientation
+        theta (cvs_nonmax): kept pixels keep their value, all others are 0.  theta=None: the object's dominant orientation (of the
+        frame select_frame chose).  Returns the same shape as `maps`: one plane, or a tuple."""
+        self._caller_check("cvs_nonmax")
+        single, ms = self._plane_list(maps, 3, "nonmax")
+        outs = [self._new_like(m) for m in ms] if out is None else ([out] if single else list(out))
+        if len(outs) != len(ms):
+            raise ValueError("out: one plane per map")
+        self._bind_stream(*ms, *outs, *([] if theta is None else [theta]))
+        n = len(ms)
+        pin, pout = (Plane * n)(*[_plane(m) for m in ms]), (Plane * n)(*[_plane(o) for o in outs])
+        pt = None if theta is None else C.byref(_plane(theta))
+        self._check(lib().cvs_nonmax(self._h, pt, n, pin, pout), "cvs_nonmax")
+        return outs[0] if single else tuple(outs)
+
+    def hysteresis(self, maps, low, high, dtype=torch.uint8 if torch is not None else np.uint8, out=None, return_passes=False):
+        """8-connected hysteresis (cvs_hysteresis): 255 where a pixel is > high, or in (low, high] and connected through such pixels to
+        one > high; 0 elsewhere.  maps: one plane or a sequence; dtype uint8 (bytes) or float32 (0.0 / 255.0).  Returns the same shape
+        as `maps`, and with return_passes=True also the number of propagation passes run."""
+        self._caller_check("cvs_hysteresis")
+        single, ms = self._plane_list(maps, 1 << 30, "hysteresis")
+        u8 = self._u8_dtype(dtype)
+        if out is None:
+            outs = []
+            for m in ms:
+                if _is_torch(m):
+                    outs.append(torch.empty(tuple(m.shape), dtype=torch.uint8 if u8 else torch.float32, device=m.device))
+                else:
+                    outs.append(np.empty(m.shape, np.uint8 if u8 else np.float32))
+        else:
+            outs = [out] if single else list(out)
+        if len(outs) != len(ms):
+            raise ValueError("out: one plane per map")
+        self._bind_stream(*ms, *outs)
+        n = len(ms)
+        pin, pout = (Plane * n)(*[_plane(m) for m in ms]), (Plane * n)(*[_plane(o) for o in outs])
+        passes = C.c_int(0)
+        self._check(lib().cvs_hysteresis(self._h, n, pin, float(low), float(high), pout, C.byref(passes)), "cvs_hysteresis")
+        res = outs[0] if single else tuple(outs)
+        return (res, passes.value) if return_passes else res
+
+    def contours(self, image, low, high):
+        """Thin, linked contours of one image: pipeline(image) -> nonmax(edges, dark, bright) on the object's own theta ->
+        hysteresis(low, high).  Returns three uint8 masks (edges, dark lines, bright lines)."""
+        maps = self.pipeline(image)
+        return self.hysteresis(self.nonmax(maps[5:8]), low, high)
+
     def set_persist(self, on):
         """pipeline()/pipeline_batch(): keep the basis + orientation planes (default, like the reference
         object) or write the requested outputs only"""

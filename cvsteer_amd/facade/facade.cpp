@@ -274,6 +274,21 @@ void SteerableFiltersG2::findBrightLines(const Mat1f& e, const Mat1f& phase, Mat
     check(cvs_find(m_handle, &pe, &pp, 0, 0, &po), "cvs_find");
 }
 
+// extension: thin `response` to its local maxima across the object's dominant orientation -- m_theta, read where it lives on the
+// device (cvs_nonmax with theta = NULL), so the lazy host copy is not needed
+void SteerableFiltersG2::nonMaxSuppression(const Mat1f& response, Mat1f& output)
+{
+    cvs_plane pr = view(response), po = out_view(output, response.rows, response.cols);
+    check(cvs_nonmax(m_handle, 0, 1, &pr, &po), "cvs_nonmax");
+}
+
+// extension: 8-connected hysteresis; 0 / 255 floats, so that the callers' convertTo(CV_8UC1) applies unchanged
+void SteerableFiltersG2::hysteresis(const Mat1f& response, float low, float high, Mat1f& output)
+{
+    cvs_plane pr = view(response), po = out_view(output, response.rows, response.cols);
+    check(cvs_hysteresis(m_handle, 1, &pr, low, high, &po, 0), "cvs_hysteresis");
+}
+
 void SteerableFiltersG2::phaseWeights(const Mat1f& phase, Mat1f& lambda, float phi, bool signum, float k)
 {
     std::lock_guard<std::mutex> lock(g_static_mutex);

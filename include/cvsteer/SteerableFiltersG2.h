@@ -53,6 +53,10 @@ public:
     void steer(const std::vector<float>& thetas, std::vector<Mat1f>& g2, std::vector<Mat1f>& h2);
     void steer(const std::vector<float>& thetas, std::vector<Mat1f>& g2, std::vector<Mat1f>& h2, std::vector<Mat1f>& e,
                std::vector<Mat1f>& magnitude, std::vector<Mat1f>& phase);
+    // contour thinning (extension): non-maximum suppression of `response` across the dominant orientation m_theta (cvs_nonmax), and
+    // 8-connected hysteresis with output 0 / 255 as floats (cvs_hysteresis) -- the callers' convertTo(CV_8UC1) applies unchanged
+    void nonMaxSuppression(const Mat1f& response, Mat1f& output);
+    void hysteresis(const Mat1f& response, float low, float high, Mat1f& output);
 
 protected:
     // the reference's protected members, same names (SteerableFiltersG2.h:62-66).  m_g1..m_h4 are the 7 tap vectors; the

@@ -268,6 +268,28 @@ int cvs_phase_weights(cvs_handle h, const cvs_plane* phase, const cvs_plane* lam
 int cvs_find(cvs_handle h, const cvs_plane* e, const cvs_plane* phase,
              const cvs_plane* edges, const cvs_plane* dark, const cvs_plane* bright);
 
+/* EXTENSION beyond the reference: thin n maps (1..3, e.g. edges / dark / bright) to the local maxima of each map across the
+ * orientation theta.  theta == NULL: the handle's own CVS_PLANE_THETA of the frame chosen by cvs_select_frame (CVS_E_STATE
+ * without orientation state).  in / out: n f32 planes each, all of the handle's image size.
+ * Contract: (c, s) = cos / sin(theta) (the ~1-ulp polynomial of the steer kernels); the direction across the contour, in (column,
+ * row) steps, is (c, -s).  With ax = |c|, ay = |s|, sx = c >= 0 ? +1 : -1, sy = s >= 0 ? -1 : +1: if ax >= ay, w = ay / ax and the
+ * forward sample is (1-w)*m[r][x+sx] + w*m[r+sy][x+sx]; otherwise w = ax / ay and it is (1-w)*m[r+sy][x] + w*m[r+sy][x+sx]; the
+ * backward sample negates both steps.  Every product and sum rounds on its own, the division is correctly rounded.  A pixel is
+ * kept when m > backward && m >= forward (one pixel of a two-pixel plateau survives) and then stores m bit for bit; every other
+ * pixel -- NaN in m, theta or a sample included -- stores 0.0f.  Neighbours outside the image read as 0.0f.
+ * n outside 1..3, or an output that overlaps an input (an output may not be an input either) or another output: CVS_E_BADARG;
+ * a plane of another size: CVS_E_SIZE; G4 with theta == NULL needs orientation state (CVS_OPT_G4_EXTENSIONS).  Host and device
+ * planes; one kernel launch for all n maps, asynchronous on the handle's stream and capturable (device planes). */
+int cvs_nonmax(cvs_handle h, const cvs_plane* theta, int n, const cvs_plane* in, const cvs_plane* out);
+/* EXTENSION: 8-connected hysteresis on n planes.  A pixel is strong if v > high, weak if low < v <= high; the output is 255 for
+ * strong pixels and for weak pixels 8-connected through weak pixels to a strong one, 0 elsewhere (NaN: never kept).
+ * out: CVS_DEPTH_U8 planes (bytes) or f32 planes (0.0f / 255.0f, for the facade).  passes (may be NULL): propagation passes run.
+ * Synchronises the handle's stream; CVS_E_UNSUPPORTED while the stream is being captured.
+ * The result is the unique fixed point of the promotion, whatever the schedule.  low > high, a NaN threshold, n < 1, outputs of
+ * mixed depth or any overlap of an output with an input or another output: CVS_E_BADARG; a plane of another size than the
+ * handle's image: CVS_E_SIZE.  Nothing is written when an argument is rejected. */
+int cvs_hysteresis(cvs_handle h, int n, const cvs_plane* in, float low, float high, const cvs_plane* out, int* passes);
+
 /* the whole caller sequence of test/test.cpp:85-90 / example/steer.cpp:86-90 for one image:
  * setup(FULL) -> steer(theta_dom, g2,h2,e,mag,phase) -> find*(mag|e, phase).
  * outs[8] = {g2, h2, e, magnitude, phase, edges, dark, bright}; any entry may be NULL.
