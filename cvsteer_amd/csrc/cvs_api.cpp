@@ -1,51 +1,29 @@
-// cvs_api.cpp -- the C ABI of libcvsteer_hip.so (declared in include/cvsteer_hip.h).
+// cvs_api.cpp -- the C ABI of libcvsteer_hip.so (declared in include/cvsteer_hip.h) but for the caller pipeline (cvs_pipeline.cpp)
+// and the multi-GPU batch layer (cvs_batch.cpp): handles and options, the setup calls and do_setup behind them, state access, steering,
+// the per-pixel stages and contour thinning.
 //
-// Thin by design: argument checks, device-state ownership, host<->device staging when a
-// caller hands over host planes, and kernel dispatch.  All arithmetic on the hot path is in
-// the HIP kernels (cvs_kernels_basis.hip, cvs_kernels_point.hip); the only host arithmetic is
-// what the reference also does on the host before it touches an image: tap generation and the
-// scalar steering weights of a given theta (cvs_taps.cpp).  No CPU fallback exists.
+// Argument checks, device-state ownership, host<->device staging when a caller hands over host planes, and kernel dispatch.  All
+// arithmetic on the hot path is in the HIP kernels; the only host arithmetic is what the reference also does on the host before it
+// touches an image: tap generation and the scalar steering weights of a given theta (cvs_taps.cpp).  No CPU fallback exists.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
-#include <atomic>
-#include <chrono>
-#include <condition_variable>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <limits>
-#include <map>
-#include <mutex>
-#include <set>
-#include <tuple>
 #include <new>
-#include <string>
-#include <thread>
 #include <vector>
 
 #include "cvs_contour.h"
 #include "cvs_context.h"
+#include "cvs_layout.h"
 
 using namespace cvs;
 
-namespace {
-
-// 8-bit outputs of a three-maps launch (BasisArgs::u8_mode): 1 = gain, the output planes are the caller's bytes; 2 = normalise, the
-// outputs are f32 scratch planes and the launch reduces min / max into mm
-struct U8Req {
-    int mode;
-    float gain;
-    int* mm;
-};
-constexpr int kNotFused = 1;   // (internal status: the launch would not take a three-maps instance; nothing was launched)
-
-int do_setup(cvs_handle h, const cvs_plane* image, unsigned flags, bool steer, float theta, const cvs_plane* g,
-             const cvs_plane* hq, const cvs_plane* const* pipe_outs = nullptr, int nframes = 1, int frame = 0,
-             int out_row_lo = 0, int out_row_hi = 0, const cvs_plane* pyr = nullptr, const U8Req* u8 = nullptr)
+int cvs::do_setup(cvs_handle h, const SetupReq& rq)
 {
     if (!h) return CVS_E_BADARG;
+    const cvs_plane *image = rq.image, *g = rq.g, *hq = rq.hq, *pyr = rq.pyr;
+    unsigned flags = rq.flags;
     int rc = check_plane(h, image, "image", true);
     if (rc) return rc;
     if (pyr) {  // the next pyramid level, written by the same pass (cvs_setup_pyr)
@@ -55,32 +33,32 @@ int do_setup(cvs_handle h, const cvs_plane* image, unsigned flags, bool steer, f
     if (!(flags & CVS_SETUP_BASIS)) flags |= CVS_SETUP_BASIS;
     if ((flags & CVS_SETUP_ORIENT) && h->kind != CVS_KIND_G2 && !h->g4_ext)
         return fail(h, CVS_E_UNSUPPORTED, "the reference computes no orientation for G4 (G4.cpp:67-81); see CVS_OPT_G4_EXTENSIONS");
-    if (steer) {
+    if (rq.steer) {
         if ((rc = check_plane(h, g, "g")) || (rc = check_plane(h, hq, "hq"))) return rc;
         if ((rc = check_same(h, g, image->rows, image->cols)) || (rc = check_same(h, hq, image->rows, image->cols))) return rc;
     }
     // the kernel reads rows ahead of the rows it writes: an output that shares memory with the input would be
     // clobbered mid-flight (the reference's sepFilter2D copies in that case; here it is an error)
     {
-        const cvs_plane* outs_chk[11] = {steer ? g : nullptr, steer ? hq : nullptr};
-        for (int k = 0; k < 8; ++k) outs_chk[2 + k] = pipe_outs ? pipe_outs[k] : nullptr;
+        const cvs_plane* outs_chk[11] = {rq.steer ? g : nullptr, rq.steer ? hq : nullptr};
+        for (int k = 0; k < 8; ++k) outs_chk[2 + k] = rq.pipe_outs ? rq.pipe_outs[k] : nullptr;
         outs_chk[10] = pyr;
         if ((rc = check_no_overlap(h, image, outs_chk, 11))) return rc;
     }
     const size_t pitch = round_up((size_t)image->cols, 64);
     size_t max_pitch = std::max(pitch, is_u8(image) ? pitch : image->step / sizeof(float));
-    if (steer) max_pitch = std::max(max_pitch, std::max(g->step, hq->step) / sizeof(float));
-    if (pipe_outs)
+    if (rq.steer) max_pitch = std::max(max_pitch, std::max(g->step, hq->step) / sizeof(float));
+    if (rq.pipe_outs)
         for (int k = 0; k < 8; ++k)
-            if (pipe_outs[k]) max_pitch = std::max(max_pitch, pipe_outs[k]->step / sizeof(float));
+            if (rq.pipe_outs[k]) max_pitch = std::max(max_pitch, rq.pipe_outs[k]->step / sizeof(float));
     if (state_interleaved(h, image->rows, pitch)) max_pitch = std::max(max_pitch, pitch * (size_t)(h->kind == CVS_KIND_G4 ? 6 : 7));
     const bool may_generic = basis_may_need_scratch(h->kind, h->width, h->taps, image->rows, image->cols, max_pitch);
     const size_t scratch = may_generic ? round_up(basis_scratch_elems(h->kind, h->width, image->rows, pitch), 64) : 0;
     Call c;
     const cvs_plane* po[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (pipe_outs)
-        for (int k = 0; k < 8; ++k) po[k] = pipe_outs[k];
-    const bool u8_bytes = u8 && u8->mode == 1;   // the outputs are the caller's byte planes: nothing to stage for them
+    if (rq.pipe_outs)
+        for (int k = 0; k < 8; ++k) po[k] = rq.pipe_outs[k];
+    const bool u8_bytes = rq.u8 && rq.u8->mode == 1;   // the outputs are the caller's byte planes: nothing to stage for them
     // 8-bit images (what the reference's callers hold: test/test.cpp:73,85, example/steer.cpp:73-86) are read by the strip kernel
     // as bytes: 1 B/pix of input traffic instead of 1 B read + 4 B written by a widening pass + 4 B read
     c.u8_direct = is_u8(image) && !may_generic && !pyr;
@@ -88,7 +66,7 @@ int do_setup(cvs_handle h, const cvs_plane* image, unsigned flags, bool steer, f
     if (u8_bytes) {
         rc = begin(h, c, {c.u8_direct ? nullptr : image}, scratch + u8_stage);
     } else {
-        rc = begin(h, c, {c.u8_direct ? nullptr : image, steer ? g : nullptr, steer ? hq : nullptr, po[0], po[1], po[2], po[3], po[4], po[5], po[6], po[7], pyr},
+        rc = begin(h, c, {c.u8_direct ? nullptr : image, rq.steer ? g : nullptr, rq.steer ? hq : nullptr, po[0], po[1], po[2], po[3], po[4], po[5], po[6], po[7], pyr},
                    scratch + u8_stage);
     }
     if (rc) return rc;
@@ -97,18 +75,18 @@ int do_setup(cvs_handle h, const cvs_plane* image, unsigned flags, bool steer, f
     // 3.06 vs 3.70 ms per 4096^2 image; with an 8-bit or device image the downloads alone set the pace and the bands
     // only add per-copy overhead, 2.98 vs 2.85 ms: round 2, profiles/HISTORY_rounds_1_3.md)
     bool any_host = false;
-    for (const cvs_plane* o : {steer ? g : nullptr, steer ? hq : nullptr, po[0], po[1], po[2], po[3], po[4], po[5], po[6], po[7]})
+    for (const cvs_plane* o : {rq.steer ? g : nullptr, rq.steer ? hq : nullptr, po[0], po[1], po[2], po[3], po[4], po[5], po[6], po[7]})
         any_host = any_host || (o && o->mem == CVS_MEM_HOST);
     any_host = any_host && mem_of(image) == CVS_MEM_HOST && !is_u8(image);
     hipStreamCaptureStatus cap_st = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(h->stream, &cap_st);
-    const bool overlap = h->host_overlap && any_host && !may_generic && nframes == 1 && out_row_hi <= out_row_lo && !pyr &&
+    const bool overlap = h->host_overlap && any_host && !may_generic && rq.nframes == 1 && rq.out_row_hi <= rq.out_row_lo && !pyr &&
                          cap_st == hipStreamCaptureStatusNone && (size_t)image->rows * image->cols >= ((size_t)1 << 20) &&
                          image->rows >= 16 * (2 * h->width + 1) && !(h->kind == CVS_KIND_G4 && (flags & CVS_SETUP_ORIENT));
     c.defer = overlap;
     h->have_basis = h->have_orient = false;
-    if ((rc = ensure_state(h, image->rows, image->cols, nframes))) return rc;
-    h->cur_frame = frame;
+    if ((rc = ensure_state(h, image->rows, image->cols, rq.nframes))) return rc;
+    h->cur_frame = rq.frame;
 
     BasisArgs a{};
     PlaneRef in;
@@ -124,7 +102,7 @@ int do_setup(cvs_handle h, const cvs_plane* image, unsigned flags, bool steer, f
     // the pipeline variants keep the taller strips (round 1 shape sweep)
     // (a handle's FIRST call counts as a fresh image too: the reference's callers build one object per image,
     // example/steer.cpp:86 -- only a handle that is handed the same pointer again is re-filtering a resident image)
-    const bool fresh = h->last_image != (const void*)image->data && !pipe_outs;
+    const bool fresh = h->last_image != (const void*)image->data && !rq.pipe_outs;
     h->last_image = image->data;
     a.strip_rows = default_strip_rows(h, a.rows, a.cols, fresh);
     // New images of 24 MiB and more: the waves of the launch's first fifth of row bands also touch the rest of the image (four
@@ -143,18 +121,18 @@ int do_setup(cvs_handle h, const cvs_plane* image, unsigned flags, bool steer, f
         a.warm_k = (fresh && !pyr && in_bytes >= ((size_t)24 << 20)) ? (wk >= 0 ? wk : 4) : 0;
     }
     a.nt_stores = use_nt_stores(h, (size_t)a.rows * a.cols);
-    a.out_row_lo = out_row_lo;
-    a.out_row_hi = out_row_hi;
-    if (steer) {
+    a.out_row_lo = rq.out_row_lo;
+    a.out_row_hi = rq.out_row_hi;
+    if (rq.steer) {
         PlaneRef rg, rh;
         if ((rc = out_ref(c, g, rg)) || (rc = out_ref(c, hq, rh))) return rc;
         a.steer_g = rg.p;
         a.steer_g_pitch = rg.pitch;
         a.steer_h = rh.p;
         a.steer_h_pitch = rh.pitch;
-        host_steer_weights(h->kind, theta, a.steer_w);
+        host_steer_weights(h->kind, rq.theta, a.steer_w);
     }
-    if (pipe_outs) {
+    if (rq.pipe_outs) {
         a.pipe = 1;
         a.no_state = h->persist ? 0 : 1;
         a.find_on_e = h->find_on;
@@ -162,10 +140,10 @@ int do_setup(cvs_handle h, const cvs_plane* image, unsigned flags, bool steer, f
             if (u8_bytes) a.pipe_out[k] = po[k] ? PlaneRef{po[k]->data, po[k]->step} : PlaneRef{nullptr, 0};   // (pitch in bytes)
             else if ((rc = out_ref(c, po[k], a.pipe_out[k]))) return rc;
         }
-        if (u8) {
-            a.u8_mode = u8->mode;
-            a.u8_gain = u8->gain;
-            a.u8_mm = u8->mm;
+        if (rq.u8) {
+            a.u8_mode = rq.u8->mode;
+            a.u8_gain = rq.u8->gain;
+            a.u8_mm = rq.u8->mm;
         }
     }
     if (pyr) {
@@ -177,15 +155,15 @@ int do_setup(cvs_handle h, const cvs_plane* image, unsigned flags, bool steer, f
     float* scr = scratch ? arena_take(h, scratch) : nullptr;
     if (overlap) {
         if ((rc = host_pipeline(h, c, a, scr))) return rc;
-        h->have_basis = !(pipe_outs && !h->persist);
+        h->have_basis = !(rq.pipe_outs && !h->persist);
         h->have_orient = h->have_basis && (flags & CVS_SETUP_ORIENT) != 0;
         return CVS_OK;
     }
-    if (u8 && !basis_u8_fusable(h->kind, h->width, h->taps, a)) return kNotFused;
-    if (u8 && u8->mode == 2) HIP_TRY(h, launch_minmax_init_n(u8->mm, 3, h->stream));
+    if (rq.u8 && !basis_u8_fusable(h->kind, h->width, h->taps, a)) return kNotFused;
+    if (rq.u8 && rq.u8->mode == 2) HIP_TRY(h, launch_minmax_init_n(rq.u8->mm, 3, h->stream));
     {
         const bool orient_k = a.orient != nullptr;
-        const int variant = (orient_k ? 1 : 0) | (steer ? 2 : 0) | (a.pipe ? 4 : 0) | (a.no_state ? 8 : 0);
+        const int variant = (orient_k ? 1 : 0) | (rq.steer ? 2 : 0) | (a.pipe ? 4 : 0) | (a.no_state ? 8 : 0);
         TuneToken tok;
         if ((rc = tune_begin(h, a, variant, fresh, tok))) return rc;
         if ((a.merge_orient != 0) != (h->ngrp == 1 && h->kind == CVS_KIND_G2)) {   // the configuration wants the other grouping of the planes
@@ -208,10 +186,12 @@ int do_setup(cvs_handle h, const cvs_plane* image, unsigned flags, bool steer, f
         HIP_TRY(h, launch_point(OP_G4_ORIENT, pa, h->stream));
     }
     // a pipeline run with CVS_OPT_PERSIST_STATE = 0 wrote its outputs only: no state to address afterwards
-    h->have_basis = !(pipe_outs && !h->persist);
+    h->have_basis = !(rq.pipe_outs && !h->persist);
     h->have_orient = h->have_basis && (flags & CVS_SETUP_ORIENT) != 0;
     return finish(c);
 }
+
+namespace {
 
 void basis_inputs(cvs_handle h, PointArgs& a)
 {
@@ -277,90 +257,6 @@ int steer_common(cvs_handle h, bool map, float theta, const cvs_plane* theta_map
     a.nt_loads = a.nt_stores;  // the state planes of an image that large are not cache-resident and are read once here
     HIP_TRY(h, launch_point(op, a, h->stream));
     return finish(c);
-}
-
-// G4 caller pipeline (CVS_OPT_G4_EXTENSIONS), second stage: the pair launches have written the basis planes of `nframes` frames
-// from the current frame on; ONE per-pixel launch (k_g4_pipeline, blockIdx.z = frame) writes the orientation planes (state kept
-// only) and the requested outputs -- outs[k] is frame 0's plane k, frame z's lies out_fstride elements further (device planes;
-// host planes only with nframes = 1).  The values are those of setup(FULL) + steer_map(NULL, ...) + find(...), bit for bit.
-int g4_pipe_stage(cvs_handle h, const cvs_plane* const outs[8], int nframes, size_t out_fstride)
-{
-    Call c;
-    int rc = begin(h, c, {outs[0], outs[1], outs[2], outs[3], outs[4], outs[5], outs[6], outs[7]});
-    if (rc) return rc;
-    G4PipeArgs a{};
-    a.rows = h->rows;
-    a.cols = h->cols;
-    a.frames = nframes;
-    a.atan_mode = h->atan_mode;
-    a.find_on_e = h->find_on;
-    for (int p = 0; p < h->nb; ++p) {
-        const PlaneRef r = state_ref(h, p);
-        a.in[p] = {r.p, r.pitch, h->frame_stride};
-    }
-    if (h->persist) {   // c1, c2, c3, theta, strength: the state setup(FULL) leaves behind
-        for (int i = 0; i < 5; ++i) {
-            const PlaneRef r = state_ref(h, h->nb + i);
-            a.out[G4P_C1 + i] = {r.p, r.pitch, h->frame_stride};
-        }
-    }
-    for (int k = 0; k < 8; ++k) {
-        PlaneRef r;
-        if ((rc = out_ref(c, outs[k], r))) return rc;
-        a.out[G4P_G + k] = {r.p, r.pitch, out_fstride};
-    }
-    a.nt_stores = use_nt_stores(h, (size_t)a.rows * a.cols * nframes);
-    a.nt_loads = a.nt_stores;   // the basis planes of an image that large are not cache-resident and are read once here
-    HIP_TRY(h, launch_g4_pipeline(a, h->stream));
-    // CVS_OPT_PERSIST_STATE = 0: the basis planes were scratch for this call, nothing addressable is left
-    h->have_basis = h->have_orient = h->persist != 0;
-    return finish(c);
-}
-
-// one G4 image (frame `frame` of `nframes`): the pair launch of a basis-only setup -- the tuner key of cvs_setup(BASIS) -- and the stage
-int g4_pipeline_one(cvs_handle h, const cvs_plane* image, const cvs_plane* const outs[8], int nframes, int frame)
-{
-    const int rc = do_setup(h, image, CVS_SETUP_BASIS, false, 0.f, nullptr, nullptr, nullptr, nframes, frame);
-    return rc ? rc : g4_pipe_stage(h, outs, 1, 0);
-}
-
-// G4 frame batch (cvs_pipeline_batch, arguments checked).  f32 device frames whose outputs lie at one constant frame stride (an
-// [n, K, H, W] block, the usual case): one pair launch per frame, each writing its frame's state block, then ONE per-pixel launch
-// over all frames.  Anything else -- host or 8-bit frames, outputs anywhere -- goes frame by frame.
-int g4_pipeline_frames(cvs_handle h, const cvs_plane* images, int n, const cvs_plane* outs, bool all_dev)
-{
-    auto frame_outs = [&](int i, const cvs_plane* po[8]) {
-        for (int k = 0; k < 8; ++k) po[k] = (outs && outs[(size_t)i * 8 + k].data) ? &outs[(size_t)i * 8 + k] : nullptr;
-    };
-    bool block = all_dev;
-    ptrdiff_t d_out = 0;
-    bool have_stride = false;
-    for (int i = 1; i < n && block; ++i)
-        for (int k = 0; k < 8 && block && outs; ++k) {
-            const cvs_plane &o0 = outs[k], &oi = outs[(size_t)i * 8 + k];
-            if ((o0.data == nullptr) != (oi.data == nullptr)) block = false;
-            else if (o0.data) {
-                const ptrdiff_t dk = oi.data - o0.data;
-                if (!have_stride) { d_out = dk / i; have_stride = true; }
-                block = dk == d_out * i && d_out > 0 && oi.step == o0.step;   // (a stride of 0 would have every frame write the same planes)
-            }
-        }
-    int rc;
-    if (!block) {
-        for (int i = 0; i < n; ++i) {
-            const cvs_plane* po[8];
-            frame_outs(i, po);
-            if ((rc = g4_pipeline_one(h, &images[i], po, n, i))) return rc;
-        }
-        h->cur_frame = 0;
-        return CVS_OK;
-    }
-    for (int i = 0; i < n; ++i)
-        if ((rc = do_setup(h, &images[i], CVS_SETUP_BASIS, false, 0.f, nullptr, nullptr, nullptr, n, i))) return rc;
-    h->cur_frame = 0;
-    const cvs_plane* po[8];
-    frame_outs(0, po);
-    return g4_pipe_stage(h, po, n, (size_t)d_out);
 }
 
 }  // namespace
@@ -580,19 +476,26 @@ int cvs_sync(cvs_handle h)
 
 int cvs_setup(cvs_handle h, const cvs_plane* image, unsigned flags)
 {
-    return do_setup(h, image, flags, false, 0.f, nullptr, nullptr);
+    return do_setup(h, SetupReq{image, flags});
 }
 
 int cvs_setup_steer(cvs_handle h, const cvs_plane* image, unsigned flags, float theta, const cvs_plane* g, const cvs_plane* hq)
 {
-    return do_setup(h, image, flags, true, theta, g, hq);
+    SetupReq rq{image, flags};
+    rq.steer = true;
+    rq.theta = theta;
+    rq.g = g;
+    rq.hq = hq;
+    return do_setup(h, rq);
 }
 
 int cvs_setup_pyr(cvs_handle h, const cvs_plane* image, unsigned flags, const cvs_plane* next_level)
 {
     if (!h) return CVS_E_BADARG;
     if (!next_level) return fail(h, CVS_E_BADARG, "next_level");
-    return do_setup(h, image, flags, false, 0.f, nullptr, nullptr, nullptr, 1, 0, 0, 0, next_level);
+    SetupReq rq{image, flags};
+    rq.pyr = next_level;
+    return do_setup(h, rq);
 }
 
 // BASELINE config 3 in one call: filter every level of a Gaussian pyramid and build the pyramid on the way -- the filter launch
@@ -621,7 +524,9 @@ int cvs_pyramid_setup(cvs_handle* hs, int levels, const cvs_plane* image, unsign
         if ((rc = check_plane(h0, &level_images[l], "level image")) || (rc = check_same(h0, &level_images[l], (s->rows + 1) / 2, (s->cols + 1) / 2))) return rc;
     }
     for (int l = 0; l < levels; ++l) {
-        rc = do_setup(hs[l], level_src(l), flags, false, 0.f, nullptr, nullptr, nullptr, 1, 0, 0, 0, l + 1 < levels ? &level_images[l] : nullptr);
+        SetupReq rq{level_src(l), flags};
+        rq.pyr = l + 1 < levels ? &level_images[l] : nullptr;
+        rc = do_setup(hs[l], rq);
         if (rc) {
             if (hs[l] != h0) h0->err = hs[l]->err;
             return rc;
@@ -635,7 +540,10 @@ int cvs_setup_rows(cvs_handle h, const cvs_plane* image, unsigned flags, int row
     if (!h) return CVS_E_BADARG;
     if (!image || row_lo < 0 || row_hi > image->rows || row_lo >= row_hi) return fail(h, CVS_E_BADARG, "row range");
     if ((flags & CVS_SETUP_ORIENT) && h->kind == CVS_KIND_G4) return fail(h, CVS_E_UNSUPPORTED, "row ranges cover the basis planes only for G4");
-    return do_setup(h, image, flags, false, 0.f, nullptr, nullptr, nullptr, 1, 0, row_lo, row_hi);
+    SetupReq rq{image, flags};
+    rq.out_row_lo = row_lo;
+    rq.out_row_hi = row_hi;
+    return do_setup(h, rq);
 }
 
 static int state_index(cvs_handle h, int which)
@@ -765,17 +673,14 @@ int cvs_steer_bank(cvs_handle h, const float* thetas, int n, const cvs_plane* ou
 
     // one launch per kBankMax angles when every written plane is a device plane and each kind's planes lie at one pitch and a
     // constant stride (a [K][H][W] or [H][K][W] block, what the Python side allocates)
+    // (each kind has a stride of its own: >= 0 and a whole number of floats)
     bool one = true;
+    for (const cvs_plane* p : all) one = one && mem_of(p) == CVS_MEM_DEVICE;
     for (int o = 0; o < 5 && one; ++o) {
         if (!want[o]) continue;
-        const cvs_plane* p0 = &outs[o];
-        const ptrdiff_t d = n > 1 ? (const char*)outs[5 + o].data - (const char*)p0->data : 0;
-        one = d >= 0 && d % (ptrdiff_t)sizeof(float) == 0;
-        for (int t = 0; t < n && one; ++t) {
-            const cvs_plane* p = &outs[5 * (size_t)t + o];
-            one = mem_of(p) == CVS_MEM_DEVICE && p->step == p0->step && (const char*)p->data == (const char*)p0->data + (ptrdiff_t)t * d;
-        }
-        a.out[o] = {p0->data, p0->step / sizeof(float), (size_t)d / sizeof(float)};
+        const PlaneRun run = plane_run(n, 1, [&](int t, int) { return plane_at(outs[5 * (size_t)t + o]); }, true, sizeof(float));
+        one = run.ok;
+        a.out[o] = {outs[o].data, outs[o].step / sizeof(float), (size_t)run.stride / sizeof(float)};
     }
     if (one) {
         Call c;
@@ -1013,17 +918,8 @@ int cvs_hysteresis(cvs_handle h, int n, const cvs_plane* in, float low, float hi
     const int rows = h->rows, cols = h->cols;
     const size_t lab_pitch = round_up((size_t)cols, 64), lab_stride = round_up(lab_pitch * rows, 256);
     const size_t need = 256 + (size_t)kHystMax * lab_stride;
-    if (need > h->hy_scr_bytes) {
-        HIP_TRY(h, hipSetDevice(h->device));
-        if (h->hy_scr) {
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            HIP_TRY(h, hipFree(h->hy_scr));
-            h->hy_scr = nullptr;
-            h->hy_scr_bytes = 0;
-        }
-        HIP_TRY(h, hipMalloc(&h->hy_scr, need));
-        h->hy_scr_bytes = need;
-    }
+    if (need > h->hy_scr_bytes) HIP_TRY(h, hipSetDevice(h->device));   // (only a call that allocates sets the device: grow_scratch's own condition)
+    if ((rc = grow_scratch(h, "hipMalloc(&h->hy_scr, need)", h->hy_scr, h->hy_scr_bytes, need, 1))) return rc;
     unsigned* flag = reinterpret_cast<unsigned*>(h->hy_scr);
     // a pass that is not the last promotes at least one pixel: more passes than pixels (+ the last group) would be a fault of ours
     const long long max_passes = (long long)rows * cols * kHystMax + 64;
@@ -1090,276 +986,6 @@ int cvs_hysteresis(cvs_handle h, int n, const cvs_plane* in, float low, float hi
     return CVS_OK;
 }
 
-static int pipeline_u8(cvs_handle h, const cvs_plane* images, int n, const cvs_plane* outs, bool batch);
-static int batch_run(cvs_handle h, const cvs_plane* images, int n, const cvs_plane* outs, const U8Req* u8);
-
-int cvs_pipeline(cvs_handle h, const cvs_plane* image, const cvs_plane* const outs[8])
-{
-    if (!h || !outs) return CVS_E_BADARG;
-    if (h->kind != CVS_KIND_G2 && !h->g4_ext) return fail(h, CVS_E_UNSUPPORTED, "the caller pipeline exists for G2, and for G4 with CVS_OPT_G4_EXTENSIONS");
-    int rc = check_plane(h, image, "image", true);
-    if (rc) return rc;
-    bool any_u8 = false;
-    for (int o = 0; o < 8; ++o) {
-        if (!outs[o]) continue;
-        if ((rc = check_plane(h, outs[o], "out", true)) || (rc = check_same(h, outs[o], image->rows, image->cols))) return rc;
-        any_u8 = any_u8 || is_u8(outs[o]);
-    }
-    h->last.u8_out = 0;
-    if (any_u8) {
-        if ((rc = check_no_overlap(h, image, outs, 8))) return rc;
-        cvs_plane flat[8] = {};
-        for (int o = 0; o < 8; ++o)
-            if (outs[o]) flat[o] = *outs[o];
-        return pipeline_u8(h, image, 1, flat, false);
-    }
-    if (h->kind == CVS_KIND_G4) {   // the pair launch, then one per-pixel launch over its 11 planes
-        if ((rc = check_no_overlap(h, image, outs, 8))) return rc;
-        return g4_pipeline_one(h, image, outs, 1, 0);
-    }
-    // one launch: filter bank, orientation and the whole caller sequence in the kernel's epilogue
-    return do_setup(h, image, CVS_SETUP_FULL, false, 0.f, nullptr, nullptr, outs);
-}
-
-
-int cvs_pipeline_batch(cvs_handle h, const cvs_plane* images, int n, const cvs_plane* outs)
-{
-    if (!h || !images || n < 1) return CVS_E_BADARG;
-    if (h->kind != CVS_KIND_G2 && !h->g4_ext) return fail(h, CVS_E_UNSUPPORTED, "the caller pipeline exists for G2, and for G4 with CVS_OPT_G4_EXTENSIONS");
-    int rc;
-    const int rows = images[0].rows, cols = images[0].cols;
-    bool any_u8 = false;
-    for (int i = 0; i < n; ++i) {
-        if ((rc = check_plane(h, &images[i], "image", true)) || (rc = check_same(h, &images[i], rows, cols))) return rc;
-        for (int k = 0; outs && k < 8; ++k) {
-            const cvs_plane* o = &outs[(size_t)i * 8 + k];
-            if (!o->data) continue;
-            if ((rc = check_plane(h, o, "out", true)) || (rc = check_same(h, o, rows, cols))) return rc;
-            if (outs[k].data && is_u8(o) != is_u8(&outs[k])) return fail(h, CVS_E_BADARG, "an output has another depth than in frame 0");
-            any_u8 = any_u8 || is_u8(o);
-        }
-        if (outs) {
-            const cvs_plane* po[8];
-            for (int k = 0; k < 8; ++k) po[k] = outs[(size_t)i * 8 + k].data ? &outs[(size_t)i * 8 + k] : nullptr;
-            if ((rc = check_no_overlap(h, &images[i], po, 8))) return rc;
-        }
-    }
-    h->last.u8_out = 0;
-    if (any_u8) return pipeline_u8(h, images, n, outs, true);
-    return batch_run(h, images, n, outs, nullptr);
-}
-
-// cvs_pipeline_batch with checked arguments.  u8 (the three-maps launch with 8-bit outputs, G2): mode 1 = `outs` holds the caller's byte
-// planes, mode 2 = f32 scratch planes; kNotFused = the call would not be ONE such launch, nothing was launched.
-static int batch_run(cvs_handle h, const cvs_plane* images, int n, const cvs_plane* outs, const U8Req* u8)
-{
-    int rc;
-    const int rows = images[0].rows, cols = images[0].cols;
-    bool all_dev = true;
-    size_t max_bytes = 0;
-    for (int i = 0; i < n; ++i) {
-        all_dev = all_dev && images[i].mem == CVS_MEM_DEVICE;  // f32 on the device; 8-bit / host frames go frame by frame
-        if (!is_u8(&images[i])) max_bytes = std::max(max_bytes, (size_t)rows * images[i].step);
-        for (int k = 0; outs && k < 8; ++k) {
-            const cvs_plane* o = &outs[(size_t)i * 8 + k];
-            if (!o->data) continue;
-            all_dev = all_dev && mem_of(o) == CVS_MEM_DEVICE;
-            max_bytes = std::max(max_bytes, (size_t)rows * o->step);
-        }
-    }
-    if (h->kind == CVS_KIND_G4) return g4_pipeline_frames(h, images, n, outs, all_dev);
-    // gain mode: the byte planes of the three maps as ONE resource per frame -- frame 0's planes within 2 GiB of the lowest, a common
-    // row step, every frame at one constant byte stride; the f32 bookkeeping below then sees no outputs
-    const uint8_t* u8_lo = nullptr;
-    size_t u8_span = 0, u8_fstride = 0, u8_step = 0;
-    unsigned u8_off[8] = {};
-    if (u8 && u8->mode == 1) {
-        auto addr = [&](int i, int k) { return reinterpret_cast<const uint8_t*>(outs[(size_t)i * 8 + k].data); };
-        for (int k = 5; k < 8; ++k)
-            if (!u8_lo || addr(0, k) < u8_lo) u8_lo = addr(0, k);
-        bool ok = true;
-        for (int k = 5; k < 8; ++k) {
-            ok = ok && outs[k].step == outs[5].step;
-            u8_off[k] = (unsigned)std::min<size_t>((size_t)(addr(0, k) - u8_lo), 0xffffffffu);
-            u8_span = std::max(u8_span, (size_t)(addr(0, k) - u8_lo) + (size_t)rows * outs[5].step);
-        }
-        u8_fstride = n > 1 ? (size_t)(addr(1, 5) - addr(0, 5)) : 0;
-        for (int i = 1; i < n && ok; ++i)
-            for (int k = 5; k < 8 && ok; ++k)
-                ok = addr(i, k) > addr(0, k) && (size_t)(addr(i, k) - addr(0, k)) == u8_fstride * i && outs[(size_t)i * 8 + k].step == outs[5].step;
-        if (!ok || u8_span > (size_t)0x7ffffff0) return kNotFused;
-        u8_step = outs[5].step;
-        outs = nullptr;
-    }
-    // 8-bit frames that lie back to back on the device (a driver's upload of a block of byte images): the one-launch path
-    // below reads the bytes itself (BasisArgs::in_u8), like any regular f32 batch -- no widened copy
-    bool u8_batch = n >= 1 && images[0].mem == (CVS_MEM_DEVICE | CVS_DEPTH_U8);
-    {
-        const uint8_t* b0 = reinterpret_cast<const uint8_t*>(images[0].data);
-        for (int i = 0; i < n && u8_batch; ++i)
-            u8_batch = images[i].mem == images[0].mem && images[i].step == images[0].step &&
-                       reinterpret_cast<const uint8_t*>(images[i].data) == b0 + (size_t)i * rows * images[0].step;
-        u8_batch = u8_batch && (size_t)rows * images[0].step <= (size_t)0x7ffffff0;
-        if (u8_batch) {
-            all_dev = true;
-            for (int i = 0; i < n && all_dev; ++i)
-                for (int k = 0; outs && k < 8 && all_dev; ++k)
-                    if (outs[(size_t)i * 8 + k].data) all_dev = outs[(size_t)i * 8 + k].mem == CVS_MEM_DEVICE;
-        }
-    }
-    const size_t pitch = round_up((size_t)cols, 64);
-    // one launch over grid.z needs every plane below 2 GiB (huge frames are filtered in row bands, frame by frame)
-    const bool small_planes = std::max(max_bytes, (size_t)rows * pitch * sizeof(float)) <= (size_t)0x7ffffff0;
-    const bool fast = all_dev && small_planes &&
-                      !basis_may_need_scratch(h->kind, h->width, h->taps, rows, cols, std::max(pitch, max_bytes / sizeof(float) / rows));
-    if (!fast && u8) return kNotFused;
-    if (!fast) {
-        // host planes, tiny or huge images, non-default taps: frame by frame through the single-image path
-        for (int i = 0; i < n; ++i) {
-            const cvs_plane* po[8];
-            for (int k = 0; k < 8; ++k) po[k] = (outs && outs[(size_t)i * 8 + k].data) ? &outs[(size_t)i * 8 + k] : nullptr;
-            if ((rc = do_setup(h, &images[i], CVS_SETUP_FULL, false, 0.f, nullptr, nullptr, po, n, i))) return rc;
-        }
-        h->cur_frame = 0;
-        return CVS_OK;
-    }
-    HIP_TRY(h, hipSetDevice(h->device));
-    h->used = true;
-    h->have_basis = h->have_orient = false;
-    if ((rc = ensure_state(h, rows, cols, n))) return rc;
-    h->cur_frame = 0;
-    std::vector<BatchFrame> tab(n);
-    for (int i = 0; i < n; ++i) {
-        tab[i].in = images[i].data;
-        tab[i].in_pitch = u8_batch ? images[i].step : images[i].step / sizeof(float);   // elements of the image's own type
-        for (int k = 0; k < 8; ++k) {
-            const cvs_plane* o = outs ? &outs[(size_t)i * 8 + k] : nullptr;
-            tab[i].out[k] = (o && o->data) ? PlaneRef{o->data, o->step / sizeof(float)} : PlaneRef{nullptr, 0};
-        }
-    }
-    // Regularly strided frames -- one [n, H, W] block in, one [n, K, H, W] block out, the usual case -- need no
-    // table: frame z is frame 0 plus z strides, computed in the kernel from its arguments.  Anything else (a list
-    // of unrelated planes) goes through a device table, uploaded on the handle's stream.
-    bool regular = true;
-    ptrdiff_t d_in = 0, d_out = 0;
-    bool have_out_stride = false;
-    for (int i = 1; i < n && regular; ++i) {
-        // (8-bit frames: byte addresses, and u8_batch has already established that they lie back to back)
-        const ptrdiff_t di = u8_batch ? (ptrdiff_t)((size_t)i * rows * images[0].step) : tab[i].in - tab[0].in;
-        if (i == 1) d_in = di;
-        regular = di == d_in * i && d_in >= 0 && tab[i].in_pitch == tab[0].in_pitch;
-        for (int k = 0; k < 8 && regular; ++k) {
-            if ((tab[i].out[k].p == nullptr) != (tab[0].out[k].p == nullptr)) regular = false;
-            else if (tab[i].out[k].p) {
-                const ptrdiff_t dk = tab[i].out[k].p - tab[0].out[k].p;
-                if (!have_out_stride) { d_out = dk / i; have_out_stride = true; }
-                regular = dk == d_out * i && d_out >= 0 && tab[i].out[k].pitch == tab[0].out[k].pitch;
-            }
-        }
-    }
-    if (!regular && u8) return kNotFused;
-    if (!regular) {
-        if (n > h->frame_tab_cap) {
-            if (h->frame_tab) {
-                HIP_TRY(h, hipStreamSynchronize(h->stream));
-                HIP_TRY(h, hipFree(h->frame_tab));
-                h->frame_tab = nullptr;
-                h->frame_tab_cap = 0;
-            }
-            HIP_TRY(h, hipMalloc(&h->frame_tab, (size_t)n * sizeof(BatchFrame)));
-            h->frame_tab_cap = n;
-        }
-        // pageable source: the runtime stages it before returning, so `tab` may go out of scope
-        HIP_TRY(h, hipMemcpyAsync(h->frame_tab, tab.data(), (size_t)n * sizeof(BatchFrame), hipMemcpyHostToDevice, h->stream));
-    }
-    BasisArgs a{};
-    a.rows = rows;
-    a.cols = cols;
-    a.in_pitch = pitch;
-    a.in_u8 = u8_batch ? 1 : 0;
-    if (regular) {
-        a.batch_regular = 1;
-        a.in = tab[0].in;
-        a.in_pitch = tab[0].in_pitch;
-        a.in_frame_stride = (size_t)d_in;
-        a.out_frame_stride = (size_t)d_out;
-        for (int k = 0; k < 8; ++k) a.pipe_out[k] = tab[0].out[k];
-        // one buffer resource per frame for all outputs, if frame 0's outputs share a pitch and lie within 2 GiB
-        float* lo = nullptr;
-        size_t opitch = 0;
-        bool one = true;
-        for (int k = 0; k < 8; ++k) {
-            if (!tab[0].out[k].p) continue;
-            if (!lo || tab[0].out[k].p < lo) lo = tab[0].out[k].p;
-            if (!opitch) opitch = tab[0].out[k].pitch;
-            one = one && tab[0].out[k].pitch == opitch;
-        }
-        size_t span = 0;
-        for (int k = 0; k < 8 && one; ++k) {
-            if (!tab[0].out[k].p) continue;
-            const size_t off = (size_t)(tab[0].out[k].p - lo) * sizeof(float);
-            span = std::max(span, off + (size_t)rows * opitch * sizeof(float));
-            one = span <= (size_t)0x7ffffff0;
-            a.out_off[k] = (unsigned)off;
-            a.out_mask |= 1u << k;
-        }
-        if (one) {
-            a.out_one = 1;
-            a.out_base = lo;
-            a.out_pitch = opitch;
-            a.out_bytes = span;
-        } else {
-            a.out_mask = 0;
-        }
-    }
-    fill_state_args(h, a, true);   // frame 0 (cur_frame was reset above); frame z adds z * frame_stride in the kernel
-    a.atan_mode = h->atan_mode;
-    a.strip_rows = default_strip_rows(h, rows, cols);
-    a.nt_stores = use_nt_stores(h, (size_t)rows * cols * n);
-    a.pipe = 1;
-    a.no_state = h->persist ? 0 : 1;
-    a.find_on_e = h->find_on;
-    a.frames = regular ? nullptr : h->frame_tab;
-    a.batch = n;
-    // state kept: frames from the two halves of the batch in flight together (see k_basis); the stateless launch is bound by
-    // the SIMDs and does not care.  CVS_OPTS batch_ways=<n> is a tuning aid (1 = frames in order).
-    a.z_ways = (!a.no_state && n >= 4) ? 2 : 1;
-    // ... and on 10-row strips: round 3 sweep (profiles/r03_c4_strip_probe.txt), 32 x 1080p, five state blocks of the allocation lottery, one handle
-    // each: against 19 rows in the plain order 0.634 / 0.70 / 0.70 / 0.796 / 0.795 for 0.644 / 0.70 / 0.70 / 0.762 / 0.764 --
-    // level on the slow and middle blocks, +4.5 % on the fast ones
-    if (!a.no_state && n >= 4 && h->strip_rows <= 0) a.strip_rows = 2 * (2 * h->width + 1) - 2 * h->width;
-    if (const int ways = env_opts().batch_ways; ways > 0) a.z_ways = std::max(1, std::min(n, ways));
-    a.frame_stride = h->frame_stride;
-    // state kept: every frame is a new image -- the waves of a frame's first row bands also request the rest of the FRAME (two bands each:
-    // BasisArgs::warm_k, per frame).  32 x 1080p, same handle, alternating, sustained: +1.2 ... +2.3 % in 7 of 7 processes on three boxes
-    // (four bands +1.3 %, eight +0.3 %; profiles/r06_c4_warm.txt).  Not for the outputs-only batches (-1 %: they are bound by the SIMDs).
-    if (!a.no_state && regular && (size_t)rows * cols >= ((size_t)1 << 20)) a.warm_k = env_opts().warm >= 0 ? env_opts().warm : 2;
-    if (u8) {
-        if (u8->mode == 1) {   // the byte planes (out_pitch / out_off / out_bytes in bytes, out_base + z out_frame_stride a byte address)
-            a.out_one = 1;
-            a.out_mask = 0xE0u;
-            a.out_base = reinterpret_cast<float*>(const_cast<uint8_t*>(u8_lo));
-            a.out_pitch = u8_step;
-            a.out_bytes = u8_span;
-            a.out_frame_stride = u8_fstride;
-            for (int k = 0; k < 8; ++k) a.out_off[k] = u8_off[k];
-        }
-        a.u8_mode = u8->mode;
-        a.u8_gain = u8->gain;
-        a.u8_mm = u8->mm;
-        if (!basis_u8_fusable(h->kind, h->width, h->taps, a)) return kNotFused;
-        if (u8->mode == 2) HIP_TRY(h, launch_minmax_init_n(u8->mm, 3 * n, h->stream));
-    }
-    TuneToken tok;
-    if ((rc = tune_begin(h, a, 16 | 1 | 4 | (a.no_state ? 8 : 0), false, tok))) return rc;
-    note_launch(h, a);
-    const hipError_t le = launch_basis(h->kind, h->width, h->taps, a, nullptr, h->stream);
-    tune_end(h, tok);
-    HIP_TRY(h, le);
-    h->have_basis = h->have_orient = h->persist != 0;
-    return CVS_OK;
-}
-
 int cvs_set_u8_gain(cvs_handle h, float gain)
 {
     if (!h) return CVS_E_BADARG;
@@ -1405,333 +1031,6 @@ int cvs_pyr_down(cvs_handle h, const cvs_plane* src, const cvs_plane* dst)
     if (h->pyr_strip && launch_pyr_strip(in.p, in.pitch, src->rows, src->cols, out.p, out.pitch, h->stream, &pe)) HIP_TRY(h, pe);
     else HIP_TRY(h, launch_pyr_down(in.p, in.pitch, src->rows, src->cols, out.p, out.pitch, h->stream));
     return finish(c);
-}
-
-static int to_u8(cvs_handle h, const cvs_plane* src, uint8_t* dst, size_t dst_step, int dst_mem, bool minmax, float alpha, float beta)
-{
-    if (!h || !dst) return CVS_E_BADARG;
-    int rc = check_plane(h, src, "src");
-    if (rc) return rc;
-    if (dst_step < (size_t)src->cols) return fail(h, CVS_E_SIZE, "dst_step");
-    if (dst_mem != CVS_MEM_HOST && dst_mem != CVS_MEM_DEVICE) return fail(h, CVS_E_BADARG, "dst_mem");
-    const size_t dpitch = round_up((size_t)src->cols, 256);
-    const size_t u8_elems = dst_mem == CVS_MEM_HOST ? round_up(dpitch * src->rows / 4 + 64, 64) : 0;
-    Call c;
-    if ((rc = begin(h, c, {src}, u8_elems + (minmax ? 64 : 0)))) return rc;
-    PlaneRef in;
-    if ((rc = in_ref(c, src, in))) return rc;
-    float* mm = minmax ? arena_take(h, 64) : nullptr;   // min / max scratch from the arena (no allocation of its own, cf. to_u8_batch)
-    uint8_t* d = dst;
-    size_t dstep = dst_step;
-    if (dst_mem == CVS_MEM_HOST) {
-        d = reinterpret_cast<uint8_t*>(arena_take(h, u8_elems));
-        dstep = dpitch;
-    }
-    if (minmax) {
-        HIP_TRY(h, launch_minmax(in.p, in.pitch, src->rows, src->cols, mm, h->stream));
-        HIP_TRY(h, launch_quantize_u8(in.p, in.pitch, src->rows, src->cols, mm, d, dstep, h->stream));
-    } else {
-        HIP_TRY(h, launch_convert_u8(in.p, in.pitch, src->rows, src->cols, alpha, beta, d, dstep, h->stream));
-    }
-    if (dst_mem == CVS_MEM_DEVICE) return finish(c);
-    HIP_TRY(h, copy_rows(dst, dst_step, d, dstep, (size_t)src->cols, src->rows, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return CVS_OK;
-}
-
-// n planes at once: one min/max launch, one quantise launch, the copies to the host queued behind them and ONE
-// synchronisation -- what a driver wants that turns a rank's whole block of feature maps into files (per plane, the
-// launch + copy + sync of the single-plane call costs more than the work).  Planes that are not equally sized device
-// planes at a constant stride go one by one.
-static int to_u8_batch(cvs_handle h, const cvs_plane* src, int n, uint8_t* const* dst, size_t dst_step, int dst_mem, bool minmax, float alpha, float beta)
-{
-    if (!h || !src || !dst || n < 1) return CVS_E_BADARG;
-    if (dst_mem != CVS_MEM_HOST && dst_mem != CVS_MEM_DEVICE) return fail(h, CVS_E_BADARG, "dst_mem");
-    int rc;
-    bool regular = true;
-    const ptrdiff_t stride = n > 1 ? src[1].data - src[0].data : 0;
-    for (int i = 0; i < n; ++i) {
-        if ((rc = check_plane(h, &src[i], "src"))) return rc;
-        if (!dst[i]) return fail(h, CVS_E_BADARG, "dst");
-        regular = regular && src[i].mem == CVS_MEM_DEVICE && src[i].rows == src[0].rows && src[i].cols == src[0].cols && src[i].step == src[0].step &&
-                  src[i].data - src[0].data == stride * i;
-    }
-    if (dst_step < (size_t)src[0].cols) return fail(h, CVS_E_SIZE, "dst_step");
-    regular = regular && stride >= 0 && (size_t)src[0].rows * src[0].step <= (size_t)0x7ffffff0;
-    if (!regular) {
-        for (int i = 0; i < n; ++i)
-            if ((rc = to_u8(h, &src[i], dst[i], dst_step, dst_mem, minmax, alpha, beta))) return rc;
-        return CVS_OK;
-    }
-    const int rows = src[0].rows, cols = src[0].cols;
-    HIP_TRY(h, hipSetDevice(h->device));
-    h->used = true;
-    // scratch: 2n floats of min / max, and (host destinations) n staged byte planes
-    // host destinations that lie back to back ([n][rows][dst_step], the usual block) are staged in exactly that layout
-    // and come down as ONE linear copy (a pitched 2-D copy of the same bytes runs at a third of the link rate)
-    bool packed = dst_mem == CVS_MEM_HOST && dst_step == (size_t)cols;  // padded rows keep their padding: copied row by row
-    for (int i = 1; i < n && packed; ++i) packed = dst[i] == dst[0] + (size_t)i * rows * dst_step;
-    const size_t dpitch = packed ? dst_step : round_up((size_t)cols, 256), plane_b = dpitch * rows;
-    const size_t mm_elems = round_up((size_t)2 * n, 64);
-    const size_t stage_elems = dst_mem == CVS_MEM_HOST ? round_up(plane_b * n / 4 + 64, 64) : 0;
-    if ((rc = arena_reserve(h, mm_elems + stage_elems))) return rc;
-    h->arena_used = 0;
-    float* mm = arena_take(h, mm_elems);
-    if (dst_mem == CVS_MEM_HOST) {
-        uint8_t* stage = reinterpret_cast<uint8_t*>(arena_take(h, stage_elems));
-        HIP_TRY(h, launch_to_u8_n(src[0].data, (size_t)stride, src[0].step / sizeof(float), rows, cols, n, minmax, mm, alpha, beta, stage, plane_b, dpitch, h->stream));
-        if (packed) {
-            HIP_TRY(h, hipMemcpyAsync(dst[0], stage, plane_b * n, hipMemcpyDeviceToHost, h->stream));
-        } else {
-            for (int i = 0; i < n; ++i)
-                HIP_TRY(h, copy_rows(dst[i], dst_step, stage + (size_t)i * plane_b, dpitch, (size_t)cols, rows, hipMemcpyDeviceToHost, h->stream));
-        }
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        return CVS_OK;
-    }
-    // device destinations: regular too?  then straight into them, else plane by plane
-    const ptrdiff_t dstride = n > 1 ? dst[1] - dst[0] : 0;
-    bool dreg = dstride >= 0;
-    for (int i = 0; i < n && dreg; ++i) dreg = dst[i] - dst[0] == dstride * i;
-    if (dreg) {
-        HIP_TRY(h, launch_to_u8_n(src[0].data, (size_t)stride, src[0].step / sizeof(float), rows, cols, n, minmax, mm, alpha, beta, dst[0], (size_t)dstride, dst_step, h->stream));
-        return CVS_OK;
-    }
-    for (int i = 0; i < n; ++i)
-        if ((rc = to_u8(h, &src[i], dst[i], dst_step, dst_mem, minmax, alpha, beta))) return rc;
-    return CVS_OK;
-}
-
-int cvs_normalize_u8_batch(cvs_handle h, const cvs_plane* src, int n, uint8_t* const* dst, size_t dst_step, int dst_mem)
-{
-    return to_u8_batch(h, src, n, dst, dst_step, dst_mem, true, 0.f, 0.f);
-}
-
-int cvs_convert_u8_batch(cvs_handle h, const cvs_plane* src, int n, float alpha, float beta, uint8_t* const* dst, size_t dst_step, int dst_mem)
-{
-    return to_u8_batch(h, src, n, dst, dst_step, dst_mem, false, alpha, beta);
-}
-
-int cvs_normalize_u8(cvs_handle h, const cvs_plane* src, uint8_t* dst, size_t dst_step, int dst_mem)
-{
-    return to_u8(h, src, dst, dst_step, dst_mem, true, 0.f, 0.f);
-}
-
-int cvs_convert_u8(cvs_handle h, const cvs_plane* src, float alpha, float beta, uint8_t* dst, size_t dst_step, int dst_mem)
-{
-    return to_u8(h, src, dst, dst_step, dst_mem, false, alpha, beta);
-}
-
-// The handle's scratch for the 8-bit pipeline outputs: `slots` min / max pairs, then `planes` f32 planes of rows x pitch (grown only;
-// the state block is never used for this: it may be parked in the process-wide cache)
-static int u8_scratch(cvs_handle h, int slots, size_t planes, int rows, size_t pitch, int** mm, float** scr)
-{
-    const size_t head = round_up((size_t)2 * slots, 64), need = head + planes * rows * pitch;
-    if (need > h->u8_scr_elems) {
-        if (h->u8_scr) {
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            HIP_TRY(h, hipFree(h->u8_scr));
-            h->u8_scr = nullptr;
-            h->u8_scr_elems = 0;
-        }
-        HIP_TRY(h, hipMalloc(&h->u8_scr, need * sizeof(float)));
-        h->u8_scr_elems = need;
-    }
-    *mm = reinterpret_cast<int*>(h->u8_scr);
-    *scr = h->u8_scr + head;
-    return CVS_OK;
-}
-
-// Normalise mode, after the launch: plane i of the m f32 scratch planes (constant stride) into dst[i] with min / max pair i -- one
-// quantise launch when the destinations lie at one constant stride with one step, else one per plane
-static int quantize_planes(cvs_handle h, const float* scr, size_t plane_stride, size_t pitch, int rows, int cols, int m, const int* mm,
-                           const cvs_plane* const* dst)
-{
-    bool reg = true;
-    const ptrdiff_t ds = m > 1 ? reinterpret_cast<const uint8_t*>(dst[1]->data) - reinterpret_cast<const uint8_t*>(dst[0]->data) : 0;
-    for (int i = 1; i < m && reg; ++i)
-        reg = dst[i]->step == dst[0]->step && reinterpret_cast<const uint8_t*>(dst[i]->data) - reinterpret_cast<const uint8_t*>(dst[0]->data) == ds * i;
-    if (reg && ds >= 0) {
-        HIP_TRY(h, launch_quantize_n(scr, plane_stride, pitch, rows, cols, m, mm, reinterpret_cast<uint8_t*>(dst[0]->data), (size_t)ds, dst[0]->step, h->stream));
-        return CVS_OK;
-    }
-    for (int i = 0; i < m; ++i)
-        HIP_TRY(h, launch_quantize_n(scr + (size_t)i * plane_stride, plane_stride, pitch, rows, cols, 1, mm + 2 * i, reinterpret_cast<uint8_t*>(dst[i]->data), 0,
-                                     dst[i]->step, h->stream));
-    return CVS_OK;
-}
-
-// Three maps as bytes in the filter launch (G2, no state, find on magnitude, the compatible arctangent, device planes): kNotFused when
-// the launch would not be one three-maps instance
-static int pipeline_u8_fused(cvs_handle h, const cvs_plane* images, int n, const cvs_plane* outs, bool batch)
-{
-    const int rows = images[0].rows, cols = images[0].cols;
-    const bool gain = h->u8_gain > 0.f;
-    int rc;
-    if (gain) {   // the caller's byte planes straight from the epilogue
-        const U8Req rq{1, h->u8_gain, nullptr};
-        if (batch) rc = batch_run(h, images, n, outs, &rq);
-        else {
-            const cvs_plane* po[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, &outs[5], &outs[6], &outs[7]};
-            rc = do_setup(h, images, CVS_SETUP_FULL, false, 0.f, nullptr, nullptr, po, 1, 0, 0, 0, nullptr, &rq);
-        }
-        if (rc == CVS_OK) h->last.u8_out = 1;
-        return rc;
-    }
-    // normalise: f32 maps into the handle's scratch ([n][3][rows][pitch]) with min / max reduced in the same launch, then ONE quantise launch
-    const size_t pitch = round_up((size_t)cols, 64), pstride = pitch * rows;
-    int* mm = nullptr;
-    float* scr = nullptr;
-    if ((rc = u8_scratch(h, 3 * n, (size_t)3 * n, rows, pitch, &mm, &scr))) return rc;
-    std::vector<cvs_plane> so((size_t)n * 8, cvs_plane{nullptr, 0, 0, 0, 0});
-    std::vector<const cvs_plane*> dst((size_t)3 * n);
-    for (int i = 0; i < n; ++i)
-        for (int k = 5; k < 8; ++k) {
-            so[(size_t)i * 8 + k] = cvs_plane{scr + ((size_t)i * 3 + (k - 5)) * pstride, rows, cols, pitch * sizeof(float), CVS_MEM_DEVICE};
-            dst[(size_t)i * 3 + (k - 5)] = &outs[(size_t)i * 8 + k];
-        }
-    const U8Req rq{2, 0.f, mm};
-    if (batch) rc = batch_run(h, images, n, so.data(), &rq);
-    else {
-        const cvs_plane* po[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, &so[5], &so[6], &so[7]};
-        rc = do_setup(h, images, CVS_SETUP_FULL, false, 0.f, nullptr, nullptr, po, 1, 0, 0, 0, nullptr, &rq);
-    }
-    if (rc) return rc;
-    if ((rc = quantize_planes(h, scr, pstride, pitch, rows, cols, 3 * n, mm, dst.data()))) return rc;
-    h->last.u8_out = 2;
-    return CVS_OK;
-}
-
-// Any other call with 8-bit outputs: the f32 call with scratch planes in place of the byte planes, then the quantise kernels of
-// cvs_normalize_u8 / cvs_convert_u8 (to_u8_batch) -- the same bytes, by construction.  Host byte planes come down as bytes.
-static int pipeline_u8_composed(cvs_handle h, const cvs_plane* images, int n, const cvs_plane* outs, bool batch)
-{
-    const int rows = images[0].rows, cols = images[0].cols;
-    const size_t pitch = round_up((size_t)cols, 64), pstride = pitch * rows;
-    size_t m = 0;
-    for (size_t i = 0; i < (size_t)n * 8; ++i) m += (outs[i].data && is_u8(&outs[i])) ? 1 : 0;
-    int* mm = nullptr;
-    float* scr = nullptr;
-    int rc;
-    if ((rc = u8_scratch(h, 0, m, rows, pitch, &mm, &scr))) return rc;
-    std::vector<cvs_plane> so(outs, outs + (size_t)n * 8), src;
-    std::vector<const cvs_plane*> dst;
-    for (size_t i = 0; i < (size_t)n * 8; ++i) {
-        if (!outs[i].data || !is_u8(&outs[i])) continue;
-        so[i] = cvs_plane{scr + src.size() * pstride, rows, cols, pitch * sizeof(float), CVS_MEM_DEVICE};
-        src.push_back(so[i]);
-        dst.push_back(&outs[i]);
-    }
-    if (batch) rc = cvs_pipeline_batch(h, images, n, so.data());
-    else {
-        const cvs_plane* po[8];
-        for (int k = 0; k < 8; ++k) po[k] = so[k].data ? &so[k] : nullptr;
-        rc = cvs_pipeline(h, images, po);
-    }
-    if (rc) return rc;
-    // one to_u8_batch call per (row step, memory) of the destinations -- one of them in the usual case
-    std::vector<bool> done(dst.size(), false);
-    for (size_t i = 0; i < dst.size(); ++i) {
-        if (done[i]) continue;
-        std::vector<cvs_plane> gs;
-        std::vector<uint8_t*> gd;
-        for (size_t j = i; j < dst.size(); ++j)
-            if (!done[j] && dst[j]->step == dst[i]->step && mem_of(dst[j]) == mem_of(dst[i])) {
-                gs.push_back(src[j]);
-                gd.push_back(reinterpret_cast<uint8_t*>(dst[j]->data));
-                done[j] = true;
-            }
-        const bool minmax = !(h->u8_gain > 0.f);
-        if ((rc = to_u8_batch(h, gs.data(), (int)gs.size(), gd.data(), dst[i]->step, mem_of(dst[i]), minmax, minmax ? 0.f : h->u8_gain, 0.f))) return rc;
-    }
-    h->last.u8_out = 3;
-    return CVS_OK;
-}
-
-// G4 with extensions: the pair launch of every frame, then ONE k_g4_pipeline launch over all frames that writes the three maps as bytes
-// (gain; byte planes at one constant frame stride with one row step) or as f32 scratch with their min / max reduced, followed by one
-// quantise launch (normalise).  kNotFused (before anything is launched) when the byte planes do not lie that way.
-static int g4_u8_fused(cvs_handle h, const cvs_plane* images, int n, const cvs_plane* outs)
-{
-    const int rows = images[0].rows, cols = images[0].cols;
-    const bool gain = h->u8_gain > 0.f;
-    auto addr = [&](int i, int k) { return reinterpret_cast<uint8_t*>(outs[(size_t)i * 8 + k].data); };
-    G4PipeArgs a{};
-    int* mm = nullptr;
-    float* scr = nullptr;
-    const size_t pitch = round_up((size_t)cols, 64), pstride = pitch * rows;
-    int rc;
-    if (gain) {
-        const ptrdiff_t fs = n > 1 ? addr(1, 5) - addr(0, 5) : 0;
-        for (int i = 0; i < n; ++i)
-            for (int k = 5; k < 8; ++k)
-                if (addr(i, k) - addr(0, k) != fs * i || fs < 0 || outs[(size_t)i * 8 + k].step != outs[5].step) return kNotFused;
-        for (int k = 0; k < 3; ++k) a.out[G4P_EDGES + k] = {reinterpret_cast<float*>(addr(0, 5 + k)), outs[5].step, (size_t)fs};
-        a.u8_mode = 1;
-        a.u8_gain = h->u8_gain;
-    } else {
-        if ((rc = u8_scratch(h, 3 * n, (size_t)3 * n, rows, pitch, &mm, &scr))) return rc;
-        for (int k = 0; k < 3; ++k) a.out[G4P_EDGES + k] = {scr + (size_t)k * pstride, pitch, 3 * pstride};
-        a.u8_mode = 2;
-        a.u8_mm = mm;
-    }
-    for (int i = 0; i < n; ++i)
-        if ((rc = do_setup(h, &images[i], CVS_SETUP_BASIS, false, 0.f, nullptr, nullptr, nullptr, n, i))) return rc;
-    h->cur_frame = 0;
-    a.rows = rows;
-    a.cols = cols;
-    a.frames = n;
-    a.atan_mode = h->atan_mode;
-    a.find_on_e = h->find_on;
-    for (int p = 0; p < h->nb; ++p) {
-        const PlaneRef r = state_ref(h, p);
-        a.in[p] = {r.p, r.pitch, h->frame_stride};
-    }
-    a.nt_stores = use_nt_stores(h, (size_t)rows * cols * n);
-    a.nt_loads = a.nt_stores;
-    if (mm) HIP_TRY(h, launch_minmax_init_n(mm, 3 * n, h->stream));
-    HIP_TRY(h, launch_g4_pipeline(a, h->stream));
-    h->have_basis = h->have_orient = false;   // (no state kept: CVS_OPT_PERSIST_STATE = 0)
-    if (!gain) {
-        std::vector<const cvs_plane*> dst((size_t)3 * n);
-        for (int i = 0; i < n; ++i)
-            for (int k = 0; k < 3; ++k) dst[(size_t)i * 3 + k] = &outs[(size_t)i * 8 + 5 + k];
-        if ((rc = quantize_planes(h, scr, pstride, pitch, rows, cols, 3 * n, mm, dst.data()))) return rc;
-    }
-    h->last.u8_out = gain ? 1 : 2;
-    return CVS_OK;
-}
-
-static int pipeline_u8(cvs_handle h, const cvs_plane* images, int n, const cvs_plane* outs, bool batch)
-{
-    if (h->kind == CVS_KIND_G4) {   // (extensions on: checked by the entry points)
-        bool fused = !h->persist;
-        for (int i = 0; i < n && fused; ++i) {
-            fused = mem_of(&images[i]) == CVS_MEM_DEVICE;
-            for (int k = 0; k < 8 && fused; ++k) {
-                const cvs_plane& o = outs[(size_t)i * 8 + k];
-                fused = (o.data != nullptr) == (k >= 5) && (!o.data || o.mem == (CVS_MEM_DEVICE | CVS_DEPTH_U8));
-            }
-        }
-        if (fused) {
-            const int rc = g4_u8_fused(h, images, n, outs);
-            if (rc != kNotFused) return rc;
-        }
-        return pipeline_u8_composed(h, images, n, outs, batch);
-    }
-    bool fused = h->kind == CVS_KIND_G2 && !h->persist && !h->find_on && h->atan_mode == 0;
-    for (int i = 0; i < n && fused; ++i) {
-        fused = mem_of(&images[i]) == CVS_MEM_DEVICE;
-        for (int k = 0; k < 8 && fused; ++k) {
-            const cvs_plane& o = outs[(size_t)i * 8 + k];
-            fused = (o.data != nullptr) == (k >= 5) && (!o.data || o.mem == (CVS_MEM_DEVICE | CVS_DEPTH_U8));
-        }
-    }
-    if (fused) {
-        const int rc = pipeline_u8_fused(h, images, n, outs, batch);
-        if (rc != kNotFused) return rc;
-    }
-    return pipeline_u8_composed(h, images, n, outs, batch);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // cvs_context.h -- the handle behind the C ABI and the host-side helpers its translation units share.
-// Internal: cvs_api.cpp (entry points), cvs_handle.cpp (argument checks, staging arena, state blocks), cvs_tune.cpp (launch
-// configuration), cvs_host.cpp (overlapped host path).  The public boundary is include/cvsteer_hip.h.
+// Internal: cvs_api.cpp (entry points, do_setup), cvs_pipeline.cpp (caller pipeline, 8-bit routes), cvs_handle.cpp (argument checks,
+// staging arena, state blocks), cvs_tune.cpp (launch configuration), cvs_host.cpp (overlapped host path); cvs_layout.h (how planes lie
+// in memory) stands apart: no handle, no device.  The public boundary is include/cvsteer_hip.h.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -102,6 +103,9 @@ struct RelaxedCapture {
     RelaxedCapture& operator=(const RelaxedCapture&) = delete;
 };
 
+// the most bytes one buffer resource of a launch may span (lane offsets stay below 2 GiB): kMaxPlaneBytes of cvs_kernels_basis.hip
+constexpr size_t kMaxResourceBytes = 0x7ffffff0;
+
 inline size_t round_up(size_t v, size_t m) { return (v + m - 1) / m * m; }
 inline bool is_u8(const cvs_plane* p) { return (p->mem & CVS_DEPTH_U8) != 0; }
 inline int mem_of(const cvs_plane* p) { return p->mem & 0xff; }
@@ -135,6 +139,21 @@ int check_point_overlaps(cvs_handle h, std::initializer_list<const cvs_plane*> i
 int check_same(cvs_handle h, const cvs_plane* p, int rows, int cols);
 int arena_reserve(cvs_handle h, size_t elems);
 float* arena_take(cvs_handle h, size_t elems);
+// grow-only device memory of a handle (staging arena, frame table, 8-bit maps, hysteresis labels; cvs_destroy frees them): at least `need`
+// units of `unit` bytes at p.  Work queued on the old block finishes before it is freed.  `what` names the allocation in cvs_last_error.
+template <class T, class N>
+int grow_scratch(cvs_handle h, const char* what, T*& p, N& cap, N need, size_t unit)
+{
+    if (need <= cap) return CVS_OK;
+    hipError_t e = hipSuccess;
+    if (p && (e = hipStreamSynchronize(h->stream)) == hipSuccess) e = hipFree(p);
+    if (e != hipSuccess) return fail_hip(h, e, what);
+    p = nullptr;
+    cap = 0;
+    if ((e = hipMalloc(&p, (size_t)need * unit)) != hipSuccess) return fail_hip(h, e, what);
+    cap = need;
+    return CVS_OK;
+}
 size_t u8_stage_elems(const cvs_plane* p);
 size_t staged_elems(const cvs_plane* p);
 int in_ref(Call& c, const cvs_plane* p, PlaneRef& r);
@@ -176,5 +195,29 @@ void note_launch(cvs_handle h, const BasisArgs& a);
 
 // ---- cvs_host.cpp ----
 int host_pipeline(cvs_handle h, Call& c, BasisArgs& a, float* scr);
+
+// ---- cvs_api.cpp ----
+// 8-bit outputs of a three-maps launch (BasisArgs::u8_mode): 1 = gain, the output planes are the caller's bytes; 2 = normalise, the
+// outputs are f32 scratch planes and the launch reduces min / max into mm
+struct U8Req {
+    int mode;
+    float gain;
+    int* mm;
+};
+constexpr int kNotFused = 1;   // (internal status: the launch would not take a three-maps instance; nothing was launched)
+// one basis launch of one image and what it writes besides the state
+struct SetupReq {
+    const cvs_plane* image = nullptr;
+    unsigned flags = 0;                              // CVS_SETUP_*
+    bool steer = false;                              // scalar steer in the epilogue: g, hq at theta
+    float theta = 0.f;
+    const cvs_plane *g = nullptr, *hq = nullptr;
+    const cvs_plane* const* pipe_outs = nullptr;     // the caller pipeline's eight outputs (any may be null)
+    int nframes = 1, frame = 0;                      // the state holds nframes blocks, this image is block `frame`
+    int out_row_lo = 0, out_row_hi = 0;              // lo < hi: only these rows are written (cvs_setup_rows)
+    const cvs_plane* pyr = nullptr;                  // the next pyramid level, written by the same pass
+    const U8Req* u8 = nullptr;                       // with pipe_outs: 8-bit three-maps launch, or kNotFused
+};
+int do_setup(cvs_handle h, const SetupReq& rq);
 
 }  // namespace cvs

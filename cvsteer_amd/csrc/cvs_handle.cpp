@@ -152,16 +152,7 @@ int check_same(cvs_handle h, const cvs_plane* p, int rows, int cols)
 
 int arena_reserve(cvs_handle h, size_t elems)
 {
-    if (elems <= h->arena_elems) return CVS_OK;
-    if (h->arena) {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        HIP_TRY(h, hipFree(h->arena));
-        h->arena = nullptr;
-        h->arena_elems = 0;
-    }
-    HIP_TRY(h, hipMalloc(&h->arena, elems * sizeof(float)));
-    h->arena_elems = elems;
-    return CVS_OK;
+    return grow_scratch(h, "hipMalloc(&h->arena, elems * sizeof(float))", h->arena, h->arena_elems, elems, sizeof(float));
 }
 
 float* arena_take(cvs_handle h, size_t elems)
@@ -434,7 +425,7 @@ void release_state(cvs_handle h)
 // twelve planes in one group must still lie within the 32-bit buffer offsets of one launch
 bool state_merge_fits(cvs_handle h, int rows, size_t dense_pitch)
 {
-    return h->kind == CVS_KIND_G2 && (size_t)rows * dense_pitch * sizeof(float) * (size_t)(h->nb + 5) <= (size_t)0x7ffffff0;
+    return h->kind == CVS_KIND_G2 && (size_t)rows * dense_pitch * sizeof(float) * (size_t)(h->nb + 5) <= kMaxResourceBytes;
 }
 
 void layout_state(cvs_handle h, bool merge_orient)
@@ -477,7 +468,7 @@ void layout_state(cvs_handle h, bool merge_orient)
 // within the 32-bit buffer offsets of one launch (larger states -- 8192^2 G4, 16384^2 G2 -- stay planar and are banded)
 bool state_interleaved(cvs_handle h, int rows, size_t dense_pitch)
 {
-    return h->layout >= 1 && (size_t)rows * dense_pitch * sizeof(float) * (size_t)(h->kind == CVS_KIND_G4 ? 6 : 7) <= (size_t)0x7ffffff0;
+    return h->layout >= 1 && (size_t)rows * dense_pitch * sizeof(float) * (size_t)(h->kind == CVS_KIND_G4 ? 6 : 7) <= kMaxResourceBytes;
 }
 
 int ensure_state(cvs_handle h, int rows, int cols, int nframes)

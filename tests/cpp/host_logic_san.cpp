@@ -1,7 +1,8 @@
 // host_logic_san.cpp -- the host logic of libcvsteer_hip.so that needs no device, under AddressSanitizer +
 // UndefinedBehaviorSanitizer: argument checks (check_plane), the overlap rules of include/cvsteer_hip.h (planes_overlap against
 // a byte-for-byte model on random views), the CVS_OPTS parser on hostile strings, the state layout arithmetic (layout_state on
-// every kind / size / grouping: offsets inside the block, no two planes sharing an element) and the tap generator.  A cvs_context is
+// every kind / size / grouping: offsets inside the block, no two planes sharing an element), the plane-run and one-resource classifier
+// of cvs_layout.h (a table of layouts with the answer every call site gave before it existed) and the tap generator.  A cvs_context is
 // a plain struct: it is built here without a HIP call; no entry point that touches the device is called.
 // Built and run by tools/run_sanitizers.sh and tests/test_sanitizers_cpu.py:
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude -Icvsteer_amd/csrc -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include \
@@ -14,6 +15,7 @@
 #include <vector>
 
 #include "cvs_context.h"
+#include "cvs_layout.h"
 
 namespace cvs {
 // the two kernel-side symbols the host objects refer to (never reached here)
@@ -142,6 +144,83 @@ int main()
                     REQUIRE(sr >= 2 * (2 * c.width + 1) - 2 * c.width && sr <= 4 * (2 * c.width + 1));
                 }
 
+    // ---- plane runs and one-resource spans (cvs_layout.h): made-up addresses, nothing is dereferenced ----
+    // One row per layout of n frames x K planes, plane k of frame i at base + i * fstride + k * pstride (+ the row's twist).  `want` is
+    // what each call site's own loop answered before the classifier existed: F = g4_pipeline_frames (stride > 0 once n > 1), R =
+    // batch_run's regular block, quantize_planes and to_u8_batch (stride >= 0), G = batch_run's gain mode (stride > 0, and frame 0 one
+    // resource), U = g4_u8_fused (stride >= 0), B = cvs_steer_bank (stride >= 0 and a whole number of floats).
+    {
+        enum Twist { NONE, FRAME2_PLUS_1, F1_K1_PLUS_4, STEP_F1_K1, ABSENT_F0_K1, ABSENT_K1 };
+        struct Row {
+            const char* name;
+            int n, K;
+            size_t step;
+            ptrdiff_t pstride, fstride;
+            Twist twist;
+            const char* want;   // F R G U B: 'y' / 'n'
+            ptrdiff_t stride;   // where accepted
+        };
+        const int rows = 16;
+        const uintptr_t base = 0x40000000u;
+        const Row table[] = {
+            {"dense [4][3][16][64] f32", 4, 3, 256, 4096, 12288, NONE, "yyyyy", 12288},
+            {"the same with padded rows", 4, 3, 320, 5120, 15360, NONE, "yyyyy", 15360},
+            {"frames further apart than their planes need", 4, 3, 256, 4096, 65536, NONE, "yyyyy", 65536},
+            {"frame 2 moved by one byte", 4, 3, 256, 4096, 12288, FRAME2_PLUS_1, "nnnnn", 0},
+            {"plane 1 alone at another stride than planes 0 and 2 (frame 1 of 2 moved by 4 bytes)", 2, 3, 256, 4096, 12288, F1_K1_PLUS_4, "nnnnn", 0},
+            {"the same with four frames", 4, 3, 256, 4096, 12288, F1_K1_PLUS_4, "nnnnn", 0},
+            {"frame 1, plane 1 with another step", 4, 3, 256, 4096, 12288, STEP_F1_K1, "nnnnn", 0},
+            {"plane 1 absent in frame 0 only", 4, 3, 256, 4096, 12288, ABSENT_F0_K1, "nnnnn", 0},
+            {"plane 1 absent in every frame", 4, 3, 256, 4096, 12288, ABSENT_K1, "yyyyy", 12288},
+            {"stride 0: every frame the same planes", 3, 3, 256, 4096, 0, NONE, "nynyy", 0},
+            {"negative stride", 3, 3, 256, 4096, -12288, NONE, "nnnnn", 0},
+            {"byte planes, stride not a multiple of 4", 3, 3, 64, 1024, 3074, NONE, "yyyyn", 3074},
+            {"n = 1", 1, 3, 256, 4096, 0, NONE, "yyyyy", 0},
+            {"n = 2", 2, 3, 256, 4096, 12288, NONE, "yyyyy", 12288},
+        };
+        const bool zero_ok[5] = {false, true, false, true, true};
+        const ptrdiff_t divisor[5] = {1, 1, 1, 1, 4};
+        for (const Row& r : table) {
+            auto at = [&](int i, int k) {
+                PlaneAt p{base + (uintptr_t)(i * r.fstride + k * r.pstride), r.step};
+                if (r.twist == FRAME2_PLUS_1 && i == 2) p.addr += 1;
+                if (r.twist == F1_K1_PLUS_4 && i == 1 && k == 1) p.addr += 4;
+                if (r.twist == STEP_F1_K1 && i == 1 && k == 1) p.step += 64;
+                if ((r.twist == ABSENT_F0_K1 && i == 0 && k == 1) || (r.twist == ABSENT_K1 && k == 1)) p = {0, 0};
+                return p;
+            };
+            for (int s = 0; s < 5; ++s) {
+                const PlaneRun run = plane_run(r.n, r.K, at, zero_ok[s], divisor[s]);
+                if (run.ok != (r.want[s] == 'y') || (run.ok && run.stride != r.stride)) {
+                    std::fprintf(stderr, "host_logic_san: plane_run: \"%s\", site %c: ok %d stride %td\n", r.name, "FRGUB"[s], (int)run.ok, run.stride);
+                    return 1;
+                }
+            }
+            // frame 0 as one resource: the lowest base, offsets k * pstride, the span up to the end of the last plane
+            PlaneAt p0[8] = {};
+            for (int k = 0; k < r.K; ++k) p0[k] = at(0, k);
+            const OneResource res = one_resource(p0, rows, kMaxResourceBytes);
+            REQUIRE(res.ok && res.base == base && res.step == r.step && res.span == (size_t)(r.K - 1) * r.pstride + rows * r.step);
+            for (int k = 0; k < r.K; ++k) REQUIRE(!p0[k].addr ? !(res.mask >> k & 1) : (res.mask >> k & 1) && res.off[k] == (unsigned)(k * r.pstride));
+        }
+        // three planes in any order, the highest ending exactly at the limit of a buffer resource, then one byte beyond it; two steps
+        // in one frame; no plane at all
+        const size_t plane = (size_t)rows * 1024;
+        PlaneAt p[8] = {{base + 4096, 1024}, {0, 0}, {base, 1024}, {0, 0}, {0, 0}, {base + kMaxResourceBytes - plane, 1024}, {0, 0}, {0, 0}};
+        OneResource res = one_resource(p, rows, kMaxResourceBytes);
+        REQUIRE(res.ok && res.span == kMaxResourceBytes && res.base == base && res.mask == 0x25u && res.off[0] == 4096 && res.off[2] == 0 &&
+                res.off[5] == (unsigned)(kMaxResourceBytes - plane));
+        p[5].addr += 1;
+        res = one_resource(p, rows, kMaxResourceBytes);
+        REQUIRE(!res.ok && res.span == kMaxResourceBytes + 1);
+        p[5] = {base + 2 * plane, 2048};
+        REQUIRE(!one_resource(p, rows, kMaxResourceBytes).ok);
+        const PlaneAt none[8] = {};
+        res = one_resource(none, rows, kMaxResourceBytes);
+        REQUIRE(res.ok && res.mask == 0 && res.span == 0 && res.base == 0);
+        static_assert(kMaxResourceBytes == 0x7ffffff0u, "the host's limit is kMaxPlaneBytes of cvs_kernels_basis.hip");
+    }
+
     // ---- taps ----
     float t[kMaxTaps];
     REQUIRE(host_make_taps(CVS_KIND_G2, 0, 4, 0.67f, t) == 0 && t[4] < 0.f && t[0] == t[8]);
@@ -149,6 +228,6 @@ int main()
     REQUIRE(host_make_taps(7, 0, 4, 0.67f, t) != 0 && host_make_taps(CVS_KIND_G2, 7, 4, 0.67f, t) != 0 && host_make_taps(CVS_KIND_G2, 0, kMaxWidth + 1, 0.67f, t) != 0);
     float w[kMaxBasis];
     for (float th : {0.f, 0.3f, -1.2f, 3.1415927f}) REQUIRE(host_steer_weights(CVS_KIND_G2, th, w) == 0 && host_steer_weights(CVS_KIND_G4, th, w) == 0);
-    std::printf("host_logic_san: argument checks, 20000 overlap cases, CVS_OPTS fuzz, 480 state layouts, taps: no sanitizer report\n");
+    std::printf("host_logic_san: argument checks, 20000 overlap cases, CVS_OPTS fuzz, 480 state layouts, 14 plane layouts, taps: no sanitizer report\n");
     return 0;
 }
