@@ -9,6 +9,7 @@ OK, E_BADARG, E_SIZE, E_HIP, E_NOMEM, E_STATE, E_UNSUPPORTED = 0, -1, -2, -3, -4
 KIND_G2, KIND_G4 = 2, 4
 MEM_HOST, MEM_DEVICE = 0, 1
 DEPTH_U8 = 0x100
+DEPTH_S32 = 0x200
 ABI_VERSION = 2
 OPT_ATAN_MODE, OPT_STRIP_ROWS, OPT_FIND_ON, OPT_G4_EXTENSIONS, OPT_BLOCK_ORDER, OPT_PERSIST_STATE = 1, 2, 3, 6, 8, 9
 OPT_AUTOTUNE = 12
@@ -38,6 +39,12 @@ class LaunchInfo(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("block_order", C.c_int32), ("strip_rows", C.c_int32), ("nt_stores", C.c_int32),
                 ("state_layout", C.c_int32), ("warm", C.c_int32), ("tuning_launches", C.c_int32), ("tuned", C.c_int32), ("tune_state", C.c_int32), ("wg_per_cu", C.c_int32), ("literal_taps", C.c_int32),
                 ("u8_out", C.c_int32)]
+
+
+class Component(C.Structure):
+    """struct cvs_component"""
+    _fields_ = [("area", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32),
+                ("first_x", C.c_int32), ("first_y", C.c_int32), ("peak_x", C.c_int32), ("peak_y", C.c_int32), ("peak", C.c_float)]
 
 
 _PP = C.POINTER(Plane)
@@ -79,6 +86,10 @@ SIGNATURES = {
     "cvs_find": (C.c_int, [C.c_void_p, _PP, _PP, _PP, _PP, _PP]),
     "cvs_nonmax": (C.c_int, [C.c_void_p, _PP, C.c_int, _PP, _PP]),
     "cvs_hysteresis": (C.c_int, [C.c_void_p, C.c_int, _PP, C.c_float, C.c_float, _PP, _IP]),
+    "cvs_label": (C.c_int, [C.c_void_p, _PP, _PP, _IP]),
+    "cvs_component_stats": (C.c_int, [C.c_void_p, _PP, C.c_int, _PP, C.c_void_p, C.c_int]),
+    "cvs_contour_prune": (C.c_int, [C.c_void_p, C.c_int, _PP, _PP, C.c_int, C.c_float, _PP, _IP]),
+    "cvs_contour_points": (C.c_int, [C.c_void_p, _PP, C.c_void_p, C.c_int, C.c_int, _IP]),
     "cvs_pipeline": (C.c_int, [C.c_void_p, _PP, C.POINTER(_PP)]),
     "cvs_pipeline_batch": (C.c_int, [C.c_void_p, _PP, C.c_int, _PP]),
     "cvs_set_u8_gain": (C.c_int, [C.c_void_p, C.c_float]),

@@ -81,7 +81,14 @@ def steer_weights(kind, theta):
 
 def _plane(a):
     """cvs_plane view of a 2-D float32 numpy array or torch CUDA tensor (no copy); 8-bit arrays /
-    tensors are accepted for input images (CVS_DEPTH_U8)."""
+    tensors are accepted for input images (CVS_DEPTH_U8), int32 ones for label planes (CVS_DEPTH_S32)."""
+    if (_is_torch(a) and a.dtype == torch.int32) or (isinstance(a, np.ndarray) and a.dtype == np.int32):
+        t = _is_torch(a)
+        if a.ndim != 2 or ((a.numel() if t else a.size) and a.shape[1] > 1 and (a.stride(1) != 1 if t else a.strides[1] != 4)):
+            raise ValueError("label plane must be 2-D int32 with unit column stride")
+        mem = (L.MEM_DEVICE if (t and a.is_cuda) else L.MEM_HOST) | L.DEPTH_S32
+        step = (a.stride(0) * 4 if t else a.strides[0]) if (a.shape[0] > 1 and a.shape[1] > 0) else a.shape[1] * 4
+        return Plane(a.data_ptr() if t else a.ctypes.data, a.shape[0], a.shape[1], step, mem)
     if _is_torch(a) and a.dtype == torch.uint8:
         if a.dim() != 2 or (a.numel() and a.shape[1] > 1 and a.stride(1) != 1):
             raise ValueError("8-bit image must be 2-D with unit column stride")
@@ -540,11 +547,113 @@ class _CallerPipeline:
         res = outs[0] if single else tuple(outs)
         return (res, passes.value) if return_passes else res
 
-    def contours(self, image, low, high):
+    # -- contour components (extension beyond the reference): cvs_label / cvs_component_stats / cvs_contour_prune / cvs_contour_points --
+    COMPONENT_DTYPE = np.dtype([("area", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("first_x", "<i4"),
+                                ("first_y", "<i4"), ("peak_x", "<i4"), ("peak_y", "<i4"), ("peak", "<f4")])
+
+    @staticmethod
+    def _new_typed_like(a, dtype_np, dtype_t):
+        if _is_torch(a):
+            return torch.empty(tuple(a.shape), dtype=dtype_t, device=a.device)
+        return np.empty(a.shape, dtype_np)
+
+    def label(self, mask, out=None):
+        """8-connected components of a mask (cvs_label): float32 (foreground: > 0) or uint8 (non-zero).  Returns (labels, count): an
+        int32 plane like `mask`, 0 for background and 1 .. count in raster order of each component's first pixel."""
+        labels = self._new_typed_like(mask, np.int32, torch.int32 if torch is not None else None) if out is None else out
+        self._bind_stream(mask, labels)
+        pm, pl = _plane(mask), _plane(labels)
+        count = C.c_int(0)
+        self._check(lib().cvs_label(self._h, C.byref(pm), C.byref(pl), C.byref(count)), "cvs_label")
+        return labels, count.value
+
+    def component_stats(self, labels, count, weight=None):
+        """One record per label 1 .. count (cvs_component_stats): a numpy structured array with the fields of `cvs_component`
+        (area, x0, y0, x1, y1, first_x, first_y, peak_x, peak_y, peak); weight: the float32 plane whose maximum is the peak."""
+        table = np.zeros(int(count), self.COMPONENT_DTYPE)
+        self._bind_stream(labels, *([] if weight is None else [weight]))
+        pl = _plane(labels)
+        pw = None if weight is None else C.byref(_plane(weight))
+        self._check(lib().cvs_component_stats(self._h, C.byref(pl), int(count), pw, C.c_void_p(table.ctypes.data if count else None),
+                                              L.MEM_HOST), "cvs_component_stats")
+        return table
+
+    def prune(self, masks, min_area, weight=None, min_peak=0.0, dtype=torch.uint8 if torch is not None else np.uint8, out=None,
+              return_kept=False):
+        """Drop the short and the faint contours (cvs_contour_prune): 255 on every 8-connected component of a mask with at least
+        min_area pixels and -- with `weight` planes -- a largest weight >= min_peak; 0 elsewhere.  masks: one plane or a sequence, like
+        hysteresis; dtype uint8 or float32.  With return_kept=True also the number of components kept (per plane)."""
+        single, ms = self._plane_list(masks, 1 << 30, "prune")
+        ws = None if weight is None else self._plane_list(weight, 1 << 30, "prune")[1]
+        if ws is not None and len(ws) != len(ms):
+            raise ValueError("weight: one plane per mask")
+        u8 = self._u8_dtype(dtype)
+        if out is None:
+            outs = [self._new_typed_like(m, np.uint8 if u8 else np.float32, (torch.uint8 if u8 else torch.float32) if torch is not None else None)
+                    for m in ms]
+        else:
+            outs = [out] if single else list(out)
+        if len(outs) != len(ms):
+            raise ValueError("out: one plane per mask")
+        self._bind_stream(*ms, *outs, *(ws or []))
+        n = len(ms)
+        pin, pout = (Plane * n)(*[_plane(m) for m in ms]), (Plane * n)(*[_plane(o) for o in outs])
+        pw = None if ws is None else (Plane * n)(*[_plane(w) for w in ws])
+        kept = (C.c_int * n)()
+        self._check(lib().cvs_contour_prune(self._h, n, pin, pw, int(min_area), float(min_peak), pout, kept), "cvs_contour_prune")
+        res = outs[0] if single else tuple(outs)
+        if return_kept:
+            return res, (kept[0] if single else list(kept))
+        return res
+
+    def contour_points(self, labels, group=False):
+        """(x, y, label) of every labelled pixel in raster order (cvs_contour_points): an (N, 3) int32 tensor / array like `labels`.
+        group=True: a stable sort by label on top, returned with the offsets -- pts[off[k - 1]:off[k]] are the pixels of contour k in
+        raster order (off has max label + 1 entries)."""
+        self._bind_stream(labels)
+        pl = _plane(labels)
+        n = C.c_int(0)
+        rc = lib().cvs_contour_points(self._h, C.byref(pl), None, 0, L.MEM_HOST, C.byref(n))
+        if rc != L.E_SIZE:
+            self._check(rc, "cvs_contour_points")
+        dev = _is_torch(labels) and labels.is_cuda
+        if dev:
+            pts = torch.empty((n.value, 3), dtype=torch.int32, device=labels.device)
+        else:
+            pts = np.empty((n.value, 3), np.int32)
+        if n.value:
+            ptr = C.c_void_p(pts.data_ptr() if dev else pts.ctypes.data)
+            self._check(lib().cvs_contour_points(self._h, C.byref(pl), ptr, n.value, L.MEM_DEVICE if dev else L.MEM_HOST, C.byref(n)),
+                        "cvs_contour_points")
+        if _is_torch(labels) and not dev:
+            pts = torch.from_numpy(pts)
+        if not group:
+            return pts
+        if _is_torch(pts):
+            order = torch.sort(pts[:, 2], stable=True).indices
+            pts = pts[order]
+            top = int(pts[-1, 2]) if len(pts) else 0
+            off = torch.zeros(top + 1, dtype=torch.int64, device=pts.device)
+            if len(pts):
+                off[1:] = torch.cumsum(torch.bincount(pts[:, 2].long(), minlength=top + 1)[1:], 0)
+        else:
+            pts = pts[np.argsort(pts[:, 2], kind="stable")]
+            top = int(pts[-1, 2]) if len(pts) else 0
+            off = np.zeros(top + 1, np.int64)
+            if len(pts):
+                off[1:] = np.cumsum(np.bincount(pts[:, 2], minlength=top + 1)[1:])
+        return pts, off
+
+    def contours(self, image, low, high, min_area=0, min_peak=0.0):
         """Thin, linked contours of one image: pipeline(image) -> nonmax(edges, dark, bright) on the object's own theta ->
-        hysteresis(low, high).  Returns three uint8 masks (edges, dark lines, bright lines)."""
+        hysteresis(low, high).  Returns three uint8 masks (edges, dark lines, bright lines).  min_area > 0 or min_peak > 0: the
+        masks are pruned on top -- components of fewer pixels, or whose strongest thinned response is below min_peak, are dropped."""
         maps = self.pipeline(image)
-        return self.hysteresis(self.nonmax(maps[5:8]), low, high)
+        thin = self.nonmax(maps[5:8])
+        masks = self.hysteresis(thin, low, high)
+        if min_area == 0 and min_peak == 0.0:
+            return masks
+        return self.prune(masks, min_area, weight=thin, min_peak=min_peak)
 
     def set_persist(self, on):
         """pipeline()/pipeline_batch(): keep the basis + orientation planes (default, like the reference

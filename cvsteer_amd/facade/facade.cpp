@@ -11,6 +11,7 @@
 #include <stdexcept>
 #include <string>
 #include <typeinfo>
+#include <vector>
 
 #include "cvsteer_hip.h"
 
@@ -64,6 +65,25 @@ Mat1f taps_of(cvs_handle h, int idx, int width)
     Mat1f k(1, 2 * width + 1);
     cvs_taps(h, idx, reinterpret_cast<float*>(k.data));
     return k;
+}
+
+// contour components (extension), shared by the G2 and G4 classes: status, or the number of components through *n
+int prune_contours(cvs_handle h, const Mat1f& mask, const Mat1f& weight, int minArea, float minPeak, Mat1f& out, int* n)
+{
+    cvs_plane pm = view(mask), pw = view(weight), po = out_view(out, mask.rows, mask.cols);
+    return cvs_contour_prune(h, 1, &pm, weight.empty() ? 0 : &pw, minArea, minPeak, &po, n);
+}
+
+int count_components(cvs_handle h, const Mat1f& mask, int* n)
+{
+    std::vector<int32_t> labels((size_t)mask.rows * (size_t)mask.cols);
+    cvs_plane pm = view(mask), pl;
+    pl.data = reinterpret_cast<float*>(labels.data());
+    pl.rows = mask.rows;
+    pl.cols = mask.cols;
+    pl.step = (size_t)mask.cols * sizeof(int32_t);
+    pl.mem = CVS_MEM_HOST | CVS_DEPTH_S32;
+    return cvs_label(h, &pm, &pl, n);
 }
 
 }  // namespace
@@ -289,6 +309,20 @@ void SteerableFiltersG2::hysteresis(const Mat1f& response, float low, float high
     check(cvs_hysteresis(m_handle, 1, &pr, low, high, &po, 0), "cvs_hysteresis");
 }
 
+int SteerableFiltersG2::pruneContours(const Mat1f& mask, const Mat1f& weight, int minArea, float minPeak, Mat1f& out)
+{
+    int n = 0;
+    check(prune_contours(m_handle, mask, weight, minArea, minPeak, out, &n), "cvs_contour_prune");
+    return n;
+}
+
+int SteerableFiltersG2::countComponents(const Mat1f& mask)
+{
+    int n = 0;
+    check(count_components(m_handle, mask, &n), "cvs_label");
+    return n;
+}
+
 void SteerableFiltersG2::phaseWeights(const Mat1f& phase, Mat1f& lambda, float phi, bool signum, float k)
 {
     std::lock_guard<std::mutex> lock(g_static_mutex);
@@ -356,6 +390,20 @@ SteerableFiltersG4::SteerableFiltersG4(const Mat1f& image, int width, float spac
     : SteerableFilters(CVS_KIND_G4, width, spacing, device)
 {
     init(image);
+}
+
+int SteerableFiltersG4::pruneContours(const Mat1f& mask, const Mat1f& weight, int minArea, float minPeak, Mat1f& out)
+{
+    int n = 0;
+    check(prune_contours(m_handle, mask, weight, minArea, minPeak, out, &n), "cvs_contour_prune");
+    return n;
+}
+
+int SteerableFiltersG4::countComponents(const Mat1f& mask)
+{
+    int n = 0;
+    check(count_components(m_handle, mask, &n), "cvs_label");
+    return n;
 }
 
 void SteerableFiltersG4::init(const Mat1f& image)

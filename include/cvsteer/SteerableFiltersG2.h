@@ -57,6 +57,11 @@ public:
     // 8-connected hysteresis with output 0 / 255 as floats (cvs_hysteresis) -- the callers' convertTo(CV_8UC1) applies unchanged
     void nonMaxSuppression(const Mat1f& response, Mat1f& output);
     void hysteresis(const Mat1f& response, float low, float high, Mat1f& output);
+    // contour components (extension): keep the 8-connected components of `mask` (foreground: > 0) with at least minArea pixels and -- unless
+    // `weight` is empty -- a largest weight >= minPeak, as 0 / 255 floats (cvs_contour_prune); returns the number kept.  countComponents:
+    // the number of 8-connected components (cvs_label)
+    int pruneContours(const Mat1f& mask, const Mat1f& weight, int minArea, float minPeak, Mat1f& out);
+    int countComponents(const Mat1f& mask);
 
 protected:
     // the reference's protected members, same names (SteerableFiltersG2.h:62-66).  m_g1..m_h4 are the 7 tap vectors; the

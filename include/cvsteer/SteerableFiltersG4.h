@@ -30,6 +30,9 @@ public:
     void getBasis(int index, Mat1f& dst) const;
     // addition: steer(thetas[k], g4[k], h4[k]) for every angle from one read of the basis planes (cvs_steer_bank)
     void steer(const std::vector<float>& thetas, std::vector<Mat1f>& g4, std::vector<Mat1f>& h4);
+    // addition: contour components, as in SteerableFiltersG2 (cvs_contour_prune / cvs_label; they read the planes passed, not the object's state)
+    int pruneContours(const Mat1f& mask, const Mat1f& weight, int minArea, float minPeak, Mat1f& out);
+    int countComponents(const Mat1f& mask);
 
 protected:
     // the reference's protected members, same names (SteerableFiltersG4.h:50-56): 11 tap vectors; the planes m_g4a..m_h4f

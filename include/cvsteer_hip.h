@@ -64,6 +64,9 @@ enum { CVS_MEM_HOST = 0, CVS_MEM_DEVICE = 1 };
  * cv::Mat1f(const Mat&) widen them unscaled (test/test.cpp:73,85; example/steer.cpp:73-86); here the 8-bit data
  * crosses PCIe as bytes and is widened on the device. */
 enum { CVS_DEPTH_U8 = 0x100 };
+/* EXTENSION (contour components): a plane of int32_t (labels); `step` in bytes, a multiple of 4, >= cols * 4.  `data` is the
+ * int32_t* cast to float*.  Accepted only where an entry point below says so. */
+enum { CVS_DEPTH_S32 = 0x200 };
 
 /* cvs_setup flags */
 enum {
@@ -289,6 +292,49 @@ int cvs_nonmax(cvs_handle h, const cvs_plane* theta, int n, const cvs_plane* in,
  * mixed depth or any overlap of an output with an input or another output: CVS_E_BADARG; a plane of another size than the
  * handle's image: CVS_E_SIZE.  Nothing is written when an argument is rejected. */
 int cvs_hysteresis(cvs_handle h, int n, const cvs_plane* in, float low, float high, const cvs_plane* out, int* passes);
+
+/* ---- EXTENSION beyond the reference: contour components -- label, measure, prune and list linked contours ----
+ * Four calls on planes of the handle's image size (CVS_E_SIZE otherwise; CVS_E_STATE before the first setup), host or device,
+ * pitched or dense, on the handle's stream; no handle state is read.  Each reads a result back: like cvs_hysteresis they
+ * synchronise the handle's stream and return CVS_E_UNSUPPORTED while it is being captured.  Nothing is written when an argument is
+ * rejected.  Every launch sequence is fixed by the image size alone, and every result is a function of the inputs alone (integer
+ * arithmetic and copies only), bit for bit.
+ * FOREGROUND of a mask plane: an f32 pixel iff v > 0.0f (NaN, zeros and negatives are background, so the outputs of cvs_hysteresis
+ * and of cvs_nonmax are masks as they stand); a CVS_DEPTH_U8 pixel iff the byte is non-zero. */
+
+/* EXTENSION: 8-connected components of `mask` into the CVS_DEPTH_S32 plane `labels`: 0 for background, components numbered
+ * 1 .. count in raster order of their first pixel (smallest row * cols + col).  count may be NULL.  labels not S32, or overlapping
+ * mask: CVS_E_BADARG; rows * cols > 2^31 - 2: CVS_E_SIZE. */
+int cvs_label(cvs_handle h, const cvs_plane* mask, const cvs_plane* labels, int* count);
+
+typedef struct cvs_component {     /* 40 bytes, all fields 4 bytes */
+    int32_t area;                  /* pixels */
+    int32_t x0, y0, x1, y1;        /* bounding box, inclusive (x = column, y = row) */
+    int32_t first_x, first_y;      /* first pixel in raster order */
+    int32_t peak_x, peak_y;        /* where `peak` is attained; the first such pixel in raster order; -1, -1 if none */
+    float peak;                    /* largest non-NaN weight over the component (-0.0f < +0.0f); -INFINITY if none */
+} cvs_component;
+/* EXTENSION: table[k - 1] describes label k of the CVS_DEPTH_S32 plane `labels`; `table` holds count entries in host or device
+ * memory (table_mem = CVS_MEM_HOST / CVS_MEM_DEVICE).  weight: an f32 plane (typically the thinned map the mask came from), or NULL:
+ * then no peak.  Pixels whose label lies outside 1 .. count are skipped; a label in 1 .. count that no pixel carries gets area 0
+ * and every position -1 (x0 = y0 = x1 = y1 = first_x = first_y = -1).  count == 0: nothing to do; count < 0, a NULL
+ * table with count > 0, labels not S32, weight not f32: CVS_E_BADARG. */
+int cvs_component_stats(cvs_handle h, const cvs_plane* labels, int count, const cvs_plane* weight,
+                        cvs_component* table, int table_mem);
+
+/* EXTENSION: for each of n >= 1 masks: label it, measure it, and write 255 to the pixels of every component with area >= min_area
+ * and (when weight != NULL) peak >= min_peak, 0 elsewhere.  out: all CVS_DEPTH_U8 or all f32 (0.0f / 255.0f), as in cvs_hysteresis.
+ * weight: NULL or n f32 planes.  kept (may be NULL) receives n ints: components kept per plane.  min_area < 0, NaN min_peak, outputs
+ * of mixed depth, any overlap of an output with an input or another output: CVS_E_BADARG. */
+int cvs_contour_prune(cvs_handle h, int n, const cvs_plane* mask, const cvs_plane* weight, int min_area,
+                      float min_peak, const cvs_plane* out, int* kept);
+
+/* EXTENSION: (x, y, label) int32 triples of all pixels of the CVS_DEPTH_S32 plane `labels` with label != 0, in raster order, into
+ * `points` (room for `capacity` triples; points_mem = CVS_MEM_HOST / CVS_MEM_DEVICE).  *n_points (required) is always set to the
+ * number of such pixels; when it exceeds capacity the call returns CVS_E_SIZE and writes no triple (capacity = 0, points = NULL
+ * sizes the buffer). */
+int cvs_contour_points(cvs_handle h, const cvs_plane* labels, int32_t* points, int capacity, int points_mem,
+                       int* n_points);
 
 /* the whole caller sequence of test/test.cpp:85-90 / example/steer.cpp:86-90 for one image:
  * setup(FULL) -> steer(theta_dom, g2,h2,e,mag,phase) -> find*(mag|e, phase).
