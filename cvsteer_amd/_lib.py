@@ -90,6 +90,9 @@ SIGNATURES = {
     "cvs_component_stats": (C.c_int, [C.c_void_p, _PP, C.c_int, _PP, C.c_void_p, C.c_int]),
     "cvs_contour_prune": (C.c_int, [C.c_void_p, C.c_int, _PP, _PP, C.c_int, C.c_float, _PP, _IP]),
     "cvs_contour_points": (C.c_int, [C.c_void_p, _PP, C.c_void_p, C.c_int, C.c_int, _IP]),
+    "cvs_link": (C.c_int, [C.c_void_p, C.c_int, _PP, C.c_float, C.c_float, C.c_int, C.c_float, _PP, C.c_void_p]),
+    "cvs_nonmax_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _PP, _PP, _PP]),
+    "cvs_contours_batch": (C.c_int, [C.c_void_p, _PP, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float, _PP]),
     "cvs_pipeline": (C.c_int, [C.c_void_p, _PP, C.POINTER(_PP)]),
     "cvs_pipeline_batch": (C.c_int, [C.c_void_p, _PP, C.c_int, _PP]),
     "cvs_set_u8_gain": (C.c_int, [C.c_void_p, C.c_float]),

@@ -655,6 +655,150 @@ class _CallerPipeline:
             return masks
         return self.prune(masks, min_area, weight=thin, min_peak=min_peak)
 
+    # -- the contour chain on the batch axis (extension): cvs_link / cvs_nonmax_batch / cvs_contours_batch --
+    @staticmethod
+    def _block_planes(t, lead):
+        """cvs_plane descriptors of the planes of a CUDA tensor whose last two axes are (H, W), filled in arithmetically: a numpy array
+        laid out like `struct cvs_plane`, one entry per index of the `lead` leading axes in C order"""
+        esz = t.element_size()
+        off = np.zeros((), np.int64)
+        for ax in range(lead):
+            shape = [1] * lead
+            shape[ax] = t.shape[ax]
+            off = off + (np.arange(t.shape[ax], dtype=np.int64) * (t.stride(ax) * esz)).reshape(shape)
+        planes = np.zeros(int(np.prod(t.shape[:lead])), _PLANE_DTYPE)
+        planes["data"] = (t.data_ptr() + np.broadcast_to(off, tuple(t.shape[:lead])).reshape(-1)).astype(np.uint64)
+        planes["rows"], planes["cols"] = int(t.shape[-2]), int(t.shape[-1])
+        planes["step"] = (t.stride(-2) if t.shape[-2] > 1 else t.shape[-1]) * esz
+        planes["mem"] = L.MEM_DEVICE | (L.DEPTH_U8 if t.dtype == torch.uint8 else 0)
+        return planes
+
+    @staticmethod
+    def _is_block(a, ndim, dtypes):
+        return _is_torch(a) and a.is_cuda and a.dim() == ndim and a.dtype in dtypes and (a.shape[-1] <= 1 or a.stride(-1) == 1)
+
+    def link(self, maps, low, high, min_area=0, min_peak=-np.inf, dtype=torch.uint8 if torch is not None else np.uint8, out=None,
+             return_kept=False):
+        """Hysteresis and prune in one labelling (cvs_link): 255 on every 8-connected component of { v > low } whose largest value is
+        > high and >= min_peak and that has at least min_area pixels, 0 elsewhere -- byte for byte hysteresis(maps, low, high) followed by
+        prune(that, min_area, weight=maps, min_peak=min_peak), without a read-back.  maps: one plane, a sequence of any length, or an
+        [N, H, W] block (a CUDA tensor: the planes are then addressed by one stride); dtype uint8 or float32.  Returns the same shape as
+        `maps`; with return_kept=True also the number of components kept per plane, as an int32 tensor on the device."""
+        self._caller_check("cvs_link")
+        u8 = self._u8_dtype(dtype)
+        if self._is_block(maps, 3, (torch.float32,) if torch is not None else ()):
+            if out is None:
+                out = torch.empty(tuple(maps.shape), dtype=torch.uint8 if u8 else torch.float32, device=maps.device)
+            if not self._is_block(out, 3, (torch.uint8, torch.float32)) or tuple(out.shape) != tuple(maps.shape):
+                raise ValueError("out: a CUDA block shaped like maps")
+            n, single, res = int(maps.shape[0]), False, out
+            self._bind_stream(maps, out)
+            pin = self._block_planes(maps, 1).ctypes.data_as(L._PP)
+            pout = self._block_planes(out, 1).ctypes.data_as(L._PP)
+            keep = (maps, out)
+        else:
+            single, ms = self._plane_list(maps, 1 << 30, "link")
+            if out is None:
+                outs = [self._new_typed_like(m, np.uint8 if u8 else np.float32, (torch.uint8 if u8 else torch.float32) if torch is not None else None)
+                        for m in ms]
+            else:
+                outs = [out] if single else list(out)
+            if len(outs) != len(ms):
+                raise ValueError("out: one plane per map")
+            self._bind_stream(*ms, *outs)
+            n = len(ms)
+            pin, pout = (Plane * n)(*[_plane(m) for m in ms]), (Plane * n)(*[_plane(o) for o in outs])
+            res = outs[0] if single else tuple(outs)
+            keep = (ms, outs)
+        kept = None
+        if return_kept:
+            if torch is None:
+                raise ValueError("return_kept: the counts stay on the device, which needs torch")
+            kept = torch.empty(n, dtype=torch.int32, device="cuda:%d" % self.device)
+            self._bind_stream(kept)
+        self._check(lib().cvs_link(self._h, n, pin, float(low), float(high), int(min_area), float(min_peak), pout,
+                                   C.c_void_p(kept.data_ptr()) if kept is not None else None), "cvs_link")
+        self._link_keepalive = keep
+        if return_kept:
+            return res, (kept[0] if single else kept)
+        return res
+
+    def nonmax_batch(self, maps, theta=None, out=None):
+        """nonmax() for F frames of K maps in one launch (cvs_nonmax_batch).  maps: an [F, K, H, W] block (K in 1..3), or a sequence of
+        F sequences of K planes; theta: [F, H, W] (or F planes), None = the dominant orientation of frames 0 .. F-1 of the last
+        pipeline_batch.  Returns / fills `out`, shaped like `maps`; every value is that of select_frame(i); nonmax(maps[i])."""
+        self._caller_check("cvs_nonmax_batch")
+        f32 = (torch.float32,) if torch is not None else ()
+        if self._is_block(maps, 4, f32):
+            if out is None:
+                out = torch.empty(tuple(maps.shape), dtype=torch.float32, device=maps.device)
+            if not self._is_block(out, 4, f32) or tuple(out.shape) != tuple(maps.shape):
+                raise ValueError("out: a CUDA block shaped like maps")
+            frames, k = int(maps.shape[0]), int(maps.shape[1])
+            pin = self._block_planes(maps, 2).ctypes.data_as(L._PP)
+            pout = self._block_planes(out, 2).ctypes.data_as(L._PP)
+            flat_in, flat_out, res = [maps], [out], out
+        else:
+            rows_in = [list(fr) for fr in maps]
+            frames, k = len(rows_in), len(rows_in[0]) if rows_in else 0
+            if frames < 1 or not 1 <= k <= 3 or any(len(fr) != k for fr in rows_in):
+                raise ValueError("nonmax_batch: F >= 1 frames of K maps each, K in 1..3")
+            rows_out = [[self._new_like(m) for m in fr] for fr in rows_in] if out is None else [list(fr) for fr in out]
+            if len(rows_out) != frames or any(len(fr) != k for fr in rows_out):
+                raise ValueError("out: one plane per map")
+            flat_in, flat_out = [m for fr in rows_in for m in fr], [o for fr in rows_out for o in fr]
+            pin = (Plane * (frames * k))(*[_plane(m) for m in flat_in])
+            pout = (Plane * (frames * k))(*[_plane(o) for o in flat_out])
+            res = out if out is not None else [tuple(fr) for fr in rows_out]
+        pt, ths = None, []
+        if theta is not None:
+            if self._is_block(theta, 3, f32):
+                if int(theta.shape[0]) != frames:
+                    raise ValueError("theta: one plane per frame")
+                ths, pt = [theta], self._block_planes(theta, 1).ctypes.data_as(L._PP)
+            else:
+                ths = list(theta)
+                if len(ths) != frames:
+                    raise ValueError("theta: one plane per frame")
+                pt = (Plane * frames)(*[_plane(t) for t in ths])
+        self._bind_stream(*flat_in, *flat_out, *ths)
+        self._check(lib().cvs_nonmax_batch(self._h, frames, k, pt, pin, pout), "cvs_nonmax_batch")
+        self._nms_keepalive = (flat_in, flat_out, ths)
+        return res
+
+    def contours_batch(self, frames, low, high, min_area=0, min_peak=0.0):
+        """contours() for n same-size frames (cvs_contours_batch): pipeline_batch -> nonmax_batch on every frame's own theta -> link.
+        frames: [n, H, W] tensor / array (float32 or uint8) or a list of planes.  Returns [n, 3, H, W] uint8 -- (edges, dark, bright) per
+        frame, each equal to contours(frame, ...) --, without a read-back for device frames; the object then holds the state of all n frames
+        (select_frame).  As in contours(), min_area == 0 and min_peak == 0.0 means no peak test."""
+        self._caller_check("cvs_contours_batch")
+        if min_area == 0 and min_peak == 0.0:
+            min_peak = -np.inf
+        if self._is_block(frames, 3, (torch.float32, torch.uint8) if torch is not None else ()):
+            planes, n = [frames], int(frames.shape[0])
+            self._like = frames[0]
+            out = torch.empty((n, 3) + tuple(frames.shape[1:]), dtype=torch.uint8, device=frames.device)
+            pim = self._block_planes(frames, 1).ctypes.data_as(L._PP)
+            pout = self._block_planes(out, 2).ctypes.data_as(L._PP)
+        else:
+            planes = [_as_input(f) for f in frames]
+            n = len(planes)
+            if n < 1:
+                raise ValueError("contours_batch: at least one frame")
+            self._like = planes[0]
+            shape = (n, 3) + tuple(planes[0].shape)
+            if _is_torch(planes[0]):
+                out = torch.empty(shape, dtype=torch.uint8, device=planes[0].device)
+            else:
+                out = np.empty(shape, np.uint8)
+            pim = (Plane * n)(*[_plane(p) for p in planes])
+            pout = (Plane * (3 * n))(*[_plane(out[i][k]) for i in range(n) for k in range(3)])
+        self._bind_stream(*planes, out)
+        self._check(lib().cvs_contours_batch(self._h, pim, n, float(low), float(high), int(min_area), float(min_peak), pout),
+                    "cvs_contours_batch")
+        self._batch_keepalive = (planes, out)
+        return out
+
     def set_persist(self, on):
         """pipeline()/pipeline_batch(): keep the basis + orientation planes (default, like the reference
         object) or write the requested outputs only"""

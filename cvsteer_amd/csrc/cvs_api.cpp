@@ -326,13 +326,14 @@ int cvs_destroy(cvs_handle h)
     (void)hipSetDevice(h->device);
     release_state(h);   // no drain: the block is parked with an event
     // staging memory exists only on handles that were given host planes, 8-bit conversions or irregular batches: those wait
-    if (h->arena || h->frame_tab || h->point_out || h->u8_scr || h->hy_scr || h->cc_scr) (void)hipStreamSynchronize(h->stream);
+    if (h->arena || h->frame_tab || h->point_out || h->u8_scr || h->hy_scr || h->cc_scr || h->ct_scr) (void)hipStreamSynchronize(h->stream);
     if (h->arena) (void)hipFree(h->arena);
     if (h->frame_tab) (void)hipFree(h->frame_tab);
     if (h->point_out) (void)hipFree(h->point_out);
     if (h->u8_scr) (void)hipFree(h->u8_scr);
     if (h->hy_scr) (void)hipFree(h->hy_scr);
     if (h->cc_scr) (void)hipFree(h->cc_scr);
+    if (h->ct_scr) (void)hipFree(h->ct_scr);
     if (h->ev_order) (void)hipEventDestroy(h->ev_order);
     for (hipEvent_t e : h->band_ev) (void)hipEventDestroy(e);
     if (h->s_up) (void)hipStreamDestroy(h->s_up);
@@ -893,6 +894,85 @@ int cvs_nonmax(cvs_handle h, const cvs_plane* theta, int n, const cvs_plane* in,
     a.nt_stores = use_nt_stores(h, (size_t)a.rows * a.cols);
     HIP_TRY(h, launch_nonmax(a, h->stream));
     return finish(c);
+}
+
+int cvs_nonmax_batch(cvs_handle h, int frames, int n_maps, const cvs_plane* theta, const cvs_plane* in, const cvs_plane* out)
+{
+    if (!h) return CVS_E_BADARG;
+    if (frames < 1 || n_maps < 1 || n_maps > kNmsMax || !in || !out) return fail(h, CVS_E_BADARG, "frames >= 1, 1..3 maps, in and out are required");
+    int rc;
+    if (!theta && (rc = need_state(h, true))) return rc;
+    if (h->rows <= 0) return fail(h, CVS_E_STATE, "no setup yet: the handle has no image size");
+    if (!theta && frames > h->num_frames) return fail(h, CVS_E_STATE, "the handle holds the state of fewer frames");
+    const int rows = h->rows, cols = h->cols;
+    const size_t np = (size_t)frames * n_maps;
+    for (int f = 0; theta && f < frames; ++f)
+        if ((rc = check_plane(h, &theta[f], "theta")) || (rc = check_same(h, &theta[f], rows, cols))) return rc;
+    for (size_t k = 0; k < np; ++k) {
+        if ((rc = check_plane(h, &in[k], "in")) || (rc = check_same(h, &in[k], rows, cols))) return rc;
+        if ((rc = check_plane(h, &out[k], "out")) || (rc = check_same(h, &out[k], rows, cols))) return rc;
+    }
+    // theta == NULL: the theta state planes of frames 0 .. frames - 1 -- an output must not overlap those either
+    std::vector<cvs_plane> own;
+    if (!theta) {
+        const PlaneRef r = state_ref(h, h->nb + 3);   // of the selected frame; frame f lies (f - cur_frame) frame strides from it
+        for (int f = 0; f < frames; ++f) {
+            cvs_plane p{};
+            p.data = r.p + ((ptrdiff_t)f - h->cur_frame) * (ptrdiff_t)h->frame_stride;
+            p.rows = rows;
+            p.cols = cols;
+            p.step = r.pitch * sizeof(float);
+            p.mem = CVS_MEM_DEVICE;
+            own.push_back(p);
+        }
+        theta = own.data();
+    }
+    std::vector<const cvs_plane*> ins;
+    for (int f = 0; f < frames; ++f) ins.push_back(&theta[f]);
+    for (size_t k = 0; k < np; ++k) ins.push_back(&in[k]);
+    if ((rc = contour_overlaps(h, ins, out, (int)np))) return rc;
+
+    // one launch when every plane is on the device and frame f's planes lie f strides behind frame 0's (an [F][K][H][W] block, the
+    // state blocks of a batch); otherwise frame by frame, the single-frame launch
+    bool dev = true;
+    for (int f = 0; f < frames; ++f) dev = dev && mem_of(&theta[f]) == CVS_MEM_DEVICE;
+    for (size_t k = 0; k < np; ++k) dev = dev && mem_of(&in[k]) == CVS_MEM_DEVICE && mem_of(&out[k]) == CVS_MEM_DEVICE;
+    const ptrdiff_t f32 = (ptrdiff_t)sizeof(float);
+    PlaneRun t_run{false, 0}, i_run[kNmsMax], o_run[kNmsMax];
+    bool regular = dev && frames <= 65535;
+    if (regular) {
+        t_run = plane_run(frames, 1, [&](int i, int) { return plane_at(theta[i]); }, true, f32);
+        regular = t_run.ok;
+        for (int k = 0; k < n_maps && regular; ++k) {
+            i_run[k] = plane_run(frames, 1, [&](int i, int) { return plane_at(in[(size_t)i * n_maps + k]); }, true, f32);
+            o_run[k] = plane_run(frames, 1, [&](int i, int) { return plane_at(out[(size_t)i * n_maps + k]); }, false, f32);
+            regular = i_run[k].ok && o_run[k].ok;
+        }
+    }
+    if (!regular) {
+        for (int f = 0; f < frames; ++f)
+            if ((rc = cvs_nonmax(h, &theta[f], n_maps, in + (size_t)f * n_maps, out + (size_t)f * n_maps))) return rc;
+        return CVS_OK;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    h->used = true;
+    NmsArgs a{};
+    NmsBatch b{};
+    a.rows = rows;
+    a.cols = cols;
+    a.n = n_maps;
+    a.theta = {static_cast<float*>(theta[0].data), theta[0].step / sizeof(float)};
+    b.frames = frames;
+    b.theta_stride = t_run.stride / f32;
+    for (int k = 0; k < n_maps; ++k) {
+        a.in[k] = {static_cast<float*>(in[k].data), in[k].step / sizeof(float)};
+        a.out[k] = {static_cast<float*>(out[k].data), out[k].step / sizeof(float)};
+        b.in_stride[k] = i_run[k].stride / f32;
+        b.out_stride[k] = o_run[k].stride / f32;
+    }
+    a.nt_stores = use_nt_stores(h, (size_t)rows * cols * frames);
+    HIP_TRY(h, launch_nonmax_batch(a, b, h->stream));
+    return CVS_OK;
 }
 
 int cvs_hysteresis(cvs_handle h, int n, const cvs_plane* in, float low, float high, const cvs_plane* out, int* passes)

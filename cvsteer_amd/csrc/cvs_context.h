@@ -61,6 +61,9 @@ struct cvs_context {
     // partials, tables and point lists in staging; grown only, freed by cvs_destroy
     unsigned char* cc_scr = nullptr;
     size_t cc_scr_bytes = 0;
+    // contour batches (cvs_contours_batch): the three maps and the three thinned maps of every frame; grown only, freed by cvs_destroy
+    float* ct_scr = nullptr;
+    size_t ct_scr_elems = 0;
     const void* last_image = nullptr;    // input pointer of the previous setup (fresh-input heuristic)
     int layout = 1;   // CVS_OPT_STATE_LAYOUT: 0 = planar, 1 = row-interleaved (default), 2 = one group of twelve for full G2 setups
     int atan_mode = 0, strip_rows = 0, find_on = 0, block_order = -1, persist = 1, g4_ext = 0, autotune = 1;

@@ -15,6 +15,14 @@ struct NmsArgs {
     int nt_stores;             // 1 = nontemporal output stores
 };
 hipError_t launch_nonmax(const NmsArgs& a, hipStream_t s);
+// ... of `frames` frames in ONE launch (blockIdx.z = frame): `a` describes frame 0, frame z is every plane of it moved by z strides
+// (elements, >= 0; the pitches are those of frame 0).  The same body as launch_nonmax: the same values, bit for bit.
+struct NmsBatch {
+    int frames;
+    long long theta_stride;
+    long long in_stride[kNmsMax], out_stride[kNmsMax];
+};
+hipError_t launch_nonmax_batch(const NmsArgs& a, const NmsBatch& b, hipStream_t s);
 // Hysteresis over n planes (blockIdx.z): byte labels at lab + z * lab_stride (row pitch lab_pitch bytes) in device scratch; outputs
 // out8[z] (bytes, out_u8 = 1) or out32[z] (f32), out_pitch in elements of the output type.
 constexpr int kHystMax = 3;

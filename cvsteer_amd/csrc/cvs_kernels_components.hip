@@ -11,6 +11,7 @@
 // is its smallest linear index -- its first pixel in raster order -- whatever the order in which the unions happened.
 #include <hip/hip_runtime.h>
 
+#include "cvs_cc_device.h"
 #include "cvs_components.h"
 
 namespace cvs {
@@ -31,33 +32,6 @@ __device__ __forceinline__ bool mask_fg(const MaskRef& m, int y, int x)
 // with the row above.  After the barrier every pixel follows its parents to the tile-local root and stores that root's GLOBAL linear
 // index (plain stores; the launch boundary publishes them).
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ int lds_get(int* L, int i) { return __hip_atomic_load(&L[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-
-__device__ __forceinline__ int lds_find(int* L, int i)
-{
-    for (;;) {
-        const int p = lds_get(L, i);
-        if (p == i) return i;
-        i = p;
-    }
-}
-
-__device__ __forceinline__ void lds_union(int* L, int a, int b)
-{
-    for (;;) {
-        a = lds_find(L, a);
-        b = lds_find(L, b);
-        if (a == b) return;
-        if (a < b) {
-            const int t = a;
-            a = b;
-            b = t;
-        }
-        const int old = __hip_atomic_fetch_min(&L[a], b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (old == a) return;   // a was still a root: linked
-        a = old;                // somebody else linked a first: go on from there
-    }
-}
 
 __global__ __launch_bounds__(256) void k_cc_tiles(const MaskRef mask, int rows, int cols, int32_t* parent, int32_t* zero_a, uint32_t* zero_b)
 {
@@ -122,33 +96,6 @@ __global__ __launch_bounds__(256) void k_cc_tiles(const MaskRef mask, int rows, 
 // atomic (loads bypass the CU's L1 and are served where the atomics are done).  The kernel reads nothing else -- background is the -1 of
 // step 1.
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ int g_get(int32_t* P, int i) { return __hip_atomic_load(&P[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ int g_find(int32_t* P, int i)
-{
-    for (;;) {
-        const int p = g_get(P, i);
-        if (p == i) return i;
-        i = p;
-    }
-}
-
-__device__ __forceinline__ void g_union(int32_t* P, int a, int b)
-{
-    for (;;) {
-        a = g_find(P, a);
-        b = g_find(P, b);
-        if (a == b) return;
-        if (a < b) {
-            const int t = a;
-            a = b;
-            b = t;
-        }
-        const int old = __hip_atomic_fetch_min(&P[a], b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (old == a) return;
-        a = old;
-    }
-}
 
 __global__ __launch_bounds__(256) void k_cc_borders(int rows, int cols, int32_t* parent)
 {
@@ -185,15 +132,6 @@ __global__ __launch_bounds__(256) void k_cc_borders(int rows, int cols, int32_t*
 // ---------------------------------------------------------------------------------------
 // Step 3: the parent plane is final and read-only from here on (plain loads behind the launch boundary).
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ int root_of(const int32_t* P, int i)
-{
-    int p = P[i];
-    while (p != i) {
-        i = p;
-        p = P[i];
-    }
-    return i;
-}
 
 __global__ __launch_bounds__(256) void k_cc_flatten(int n, const int32_t* parent, int32_t* root)
 {
@@ -335,23 +273,6 @@ __global__ __launch_bounds__(256) void k_scan_apply(const IntPlane v, int rows, 
 // a run, the run's head issues the atomics for all of it (area += length, box from its two ends, the maximum of the peak keys from a
 // segmented shuffle reduction).  Integer atomics only: no result depends on their order.
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned ordered_bits(float f)   // monotone in f for every non-NaN f, -0.0f below +0.0f; never 0
-{
-    const unsigned u = __float_as_uint(f);
-    return (u >> 31) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ float ordered_value(unsigned o) { return __uint_as_float((o >> 31) ? (o & 0x7fffffffu) : ~o); }
-
-// the lane's run among the wave's 64 keys: head = first lane of it, end = one past its last lane
-__device__ __forceinline__ void run_of(int key, int lane, bool& head, int& end)
-{
-    const int prev = __shfl_up(key, 1, 64);
-    head = lane == 0 || prev != key;
-    const unsigned long long heads = __ballot(head);
-    const unsigned long long above = lane == 63 ? 0ull : heads & (~0ull << (lane + 1));
-    end = above ? __ffsll((long long)above) - 1 : 64;
-}
 
 __global__ __launch_bounds__(256) void k_stats_init(CcAcc* acc, int count)
 {

@@ -31,7 +31,7 @@ __device__ __forceinline__ Row3 spread(float v)
 }
 
 template <int NM, bool NT>
-__global__ __launch_bounds__(256) void k_nonmax(const NmsArgs a)
+__device__ __forceinline__ void nonmax_body(const NmsArgs& a)
 {
     const int lane = threadIdx.x & 63;
     const int tile = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -94,6 +94,27 @@ __global__ __launch_bounds__(256) void k_nonmax(const NmsArgs a)
     }
 }
 
+template <int NM, bool NT>
+__global__ __launch_bounds__(256) void k_nonmax(const NmsArgs a)
+{
+    nonmax_body<NM, NT>(a);
+}
+
+// the same body for every frame of a batch in one launch: blockIdx.z = frame, its planes those of frame 0 moved by z strides
+template <int NM, bool NT>
+__global__ __launch_bounds__(256) void k_nms_frames(const NmsArgs a0, const NmsBatch b)
+{
+    NmsArgs a = a0;
+    const long long z = blockIdx.z;
+    a.theta.p += z * b.theta_stride;
+#pragma unroll
+    for (int k = 0; k < NM; ++k) {
+        a.in[k].p += z * b.in_stride[k];
+        a.out[k].p += z * b.out_stride[k];
+    }
+    nonmax_body<NM, NT>(a);
+}
+
 template <int NM>
 static void launch_nonmax_nm(const NmsArgs& a, dim3 grid, hipStream_t s)
 {
@@ -101,22 +122,52 @@ static void launch_nonmax_nm(const NmsArgs& a, dim3 grid, hipStream_t s)
     else hipLaunchKernelGGL((k_nonmax<NM, false>), grid, dim3(256), 0, s, a);
 }
 
-hipError_t launch_nonmax(const NmsArgs& a, hipStream_t s)
+template <int NM>
+static void launch_nonmax_batch_nm(const NmsArgs& a, const NmsBatch& b, dim3 grid, hipStream_t s)
 {
-    if (a.rows <= 0 || a.cols <= 0 || a.n < 1 || a.n > kNmsMax || !a.theta.p) return hipErrorInvalidValue;
+    if (a.nt_stores) hipLaunchKernelGGL((k_nms_frames<NM, true>), grid, dim3(256), 0, s, a, b);
+    else hipLaunchKernelGGL((k_nms_frames<NM, false>), grid, dim3(256), 0, s, a, b);
+}
+
+static bool nonmax_ok(const NmsArgs& a)
+{
+    if (a.rows <= 0 || a.cols <= 0 || a.n < 1 || a.n > kNmsMax || !a.theta.p) return false;
     for (int k = 0; k < a.n; ++k)
-        if (!a.in[k].p || !a.out[k].p) return hipErrorInvalidValue;
-    NmsArgs b = a;
-    const long tiles = (a.cols + kNmsSpan - 1) / kNmsSpan;
+        if (!a.in[k].p || !a.out[k].p) return false;
+    return true;
+}
+
+// rows per strip and the grid of one frame (the decisions do not depend on the strip: any strip gives the same values)
+static dim3 nonmax_grid(NmsArgs& b, long frames)
+{
+    const long tiles = (b.cols + kNmsSpan - 1) / kNmsSpan;
     // rows per strip: enough waves to keep every CU's memory pipeline busy (~8K waves), and at least 8 rows so that the two halo
     // rows of a strip stay a small part of its reads
-    long strip = (long)a.rows * tiles / 8192;
+    long strip = (long)b.rows * tiles * frames / 8192;
     strip = strip < 8 ? 8 : strip > 64 ? 64 : strip;
     b.strip = (int)strip;
-    const dim3 grid((unsigned)((tiles + 3) / 4), (unsigned)((a.rows + strip - 1) / strip));
+    return dim3((unsigned)((tiles + 3) / 4), (unsigned)((b.rows + strip - 1) / strip), (unsigned)frames);
+}
+
+hipError_t launch_nonmax(const NmsArgs& a, hipStream_t s)
+{
+    if (!nonmax_ok(a)) return hipErrorInvalidValue;
+    NmsArgs b = a;
+    const dim3 grid = nonmax_grid(b, 1);
     if (a.n == 1) launch_nonmax_nm<1>(b, grid, s);
     else if (a.n == 2) launch_nonmax_nm<2>(b, grid, s);
     else launch_nonmax_nm<3>(b, grid, s);
+    return hipGetLastError();
+}
+
+hipError_t launch_nonmax_batch(const NmsArgs& a, const NmsBatch& nb, hipStream_t s)
+{
+    if (!nonmax_ok(a) || nb.frames < 1 || nb.frames > 65535) return hipErrorInvalidValue;
+    NmsArgs b = a;
+    const dim3 grid = nonmax_grid(b, nb.frames);
+    if (a.n == 1) launch_nonmax_batch_nm<1>(b, nb, grid, s);
+    else if (a.n == 2) launch_nonmax_batch_nm<2>(b, nb, grid, s);
+    else launch_nonmax_batch_nm<3>(b, nb, grid, s);
     return hipGetLastError();
 }
 

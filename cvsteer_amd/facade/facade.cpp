@@ -316,6 +316,13 @@ int SteerableFiltersG2::pruneContours(const Mat1f& mask, const Mat1f& weight, in
     return n;
 }
 
+// extension: hysteresis and prune in one labelling; 0 / 255 floats like both
+void SteerableFiltersG2::linkContours(const Mat1f& response, float low, float high, int minArea, float minPeak, Mat1f& output)
+{
+    cvs_plane pr = view(response), po = out_view(output, response.rows, response.cols);
+    check(cvs_link(m_handle, 1, &pr, low, high, minArea, minPeak, &po, 0), "cvs_link");
+}
+
 int SteerableFiltersG2::countComponents(const Mat1f& mask)
 {
     int n = 0;
@@ -397,6 +404,13 @@ int SteerableFiltersG4::pruneContours(const Mat1f& mask, const Mat1f& weight, in
     int n = 0;
     check(prune_contours(m_handle, mask, weight, minArea, minPeak, out, &n), "cvs_contour_prune");
     return n;
+}
+
+// extension: hysteresis and prune in one labelling; 0 / 255 floats like both
+void SteerableFiltersG4::linkContours(const Mat1f& response, float low, float high, int minArea, float minPeak, Mat1f& output)
+{
+    cvs_plane pr = view(response), po = out_view(output, response.rows, response.cols);
+    check(cvs_link(m_handle, 1, &pr, low, high, minArea, minPeak, &po, 0), "cvs_link");
 }
 
 int SteerableFiltersG4::countComponents(const Mat1f& mask)

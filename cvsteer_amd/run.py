@@ -1,6 +1,6 @@
 """cvsteer-run for MI355X: the reference's batch driver (example/steer.cpp:59-173) over the HIP engine.
 
-    python -m cvsteer_amd.run --input <image | list.txt> --output <dir> [--gain G] [--g4]
+    python -m cvsteer_amd.run --input <image | list.txt> --output <dir> [--gain G] [--g4] [--contours LOW,HIGH[,MIN_AREA[,MIN_PEAK]]]
     python -m torch.distributed.run --nproc-per-node 8 -m cvsteer_amd.run --input list.txt --output out
 
 Per image, exactly the reference's per-file body (steer.cpp:69-124): gray f32 (unscaled 0..255) ->
@@ -83,6 +83,58 @@ def process_file(engine, path, outdir, gain, ext=".png"):
     return written
 
 
+def contours_arg(text):
+    """--contours LOW,HIGH[,MIN_AREA[,MIN_PEAK]] -> (low, high, min_area, min_peak); argparse turns the errors into exit status 2"""
+    parts = text.split(",")
+    if not 2 <= len(parts) <= 4:
+        raise argparse.ArgumentTypeError("expected LOW,HIGH[,MIN_AREA[,MIN_PEAK]], not %r" % text)
+    try:
+        low, high = float(parts[0]), float(parts[1])
+        min_area = int(parts[2]) if len(parts) > 2 else 0
+        min_peak = float(parts[3]) if len(parts) > 3 else 0.0
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected numbers (MIN_AREA an integer), not %r" % text)
+    if not low <= high:   # (NaN fails the test as well)
+        raise argparse.ArgumentTypeError("LOW <= HIGH, neither NaN")
+    if min_area < 0 or min_peak != min_peak:
+        raise argparse.ArgumentTypeError("MIN_AREA >= 0, MIN_PEAK not NaN")
+    return low, high, min_area, min_peak
+
+
+def process_contours(engine, paths, outdir, contours, ext=".png", chunk=32):
+    """--contours: thin, linked contours instead of the 8-bit maps.  Files of equal size and depth go through contours_batch in chunks of
+    up to `chunk` frames (one upload, one chain of launches, one download); the three 0 / 255 masks get the names of the maps.
+    -> (files written, [(path, error)])"""
+    import torch
+    dev = torch.device("cuda", engine.device)
+    low, high, min_area, min_peak = contours
+    groups, failed, written = {}, [], []
+    for path in paths:
+        try:
+            gray = np.ascontiguousarray(read_gray(path))
+            if gray.dtype != np.uint8:
+                gray = gray.astype(np.float32)
+            groups.setdefault((gray.shape, gray.dtype.str), []).append((path, gray))
+        except Exception as exc:
+            failed.append((path, exc))
+    for items in groups.values():
+        for i in range(0, len(items), chunk):
+            part = items[i:i + chunk]
+            try:
+                frames = torch.from_numpy(np.stack([g for _, g in part])).to(dev)
+                masks = engine.contours_batch(frames, low, high, min_area, min_peak).cpu().numpy()
+                for (path, _), m in zip(part, masks):
+                    base = os.path.splitext(os.path.basename(path))[0]
+                    for u8, suffix in zip(m, ("_edges", "_lines_dark", "_lines_bright")):
+                        if outdir:
+                            dst = os.path.join(outdir, base + suffix + ext)
+                            write_u8(dst, u8)
+                            written.append(dst)
+            except Exception as exc:
+                failed.extend((path, exc) for path, _ in part)
+    return written, failed
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="cvsteer-run", description=__doc__.split("\n")[0])
     ap.add_argument("--input", required=True, help="image file, or a .txt list of image files")
@@ -90,6 +142,10 @@ def main(argv=None):
     ap.add_argument("--gain", type=float, default=0.0, help="gain for the 8-bit output (0 = min-max normalise)")
     ap.add_argument("--ext", default=".png", help="output file extension (.png, .pgm, .npy ...)")
     ap.add_argument("--g4", action="store_true", help="the G4/H4 bank (width 6, spacing 0.5, extensions on) instead of G2/H2")
+    ap.add_argument("--contours", type=contours_arg, default=None, metavar="LOW,HIGH[,MIN_AREA[,MIN_PEAK]]",
+                    help="write thin, linked contours (0 / 255 masks under the same names) instead of the 8-bit maps: hysteresis "
+                         "thresholds on the thinned maps, then components of fewer than MIN_AREA pixels or with a peak below MIN_PEAK "
+                         "are dropped; files of equal size are processed in batches")
     ap.add_argument("--verbose", action="store_true")
     args = ap.parse_args(argv)
 
@@ -109,6 +165,13 @@ def main(argv=None):
         engine = SteerableFiltersG4(None, 6, 0.5, device=local_rank, extensions=True)
     else:
         engine = SteerableFiltersG2(None, 4, 0.67, device=local_rank)
+    if args.contours is not None:   # thinning reads every frame's theta plane: the state stays on
+        written, errors = process_contours(engine, files[lo:hi], args.output, args.contours, args.ext)
+        if args.verbose:
+            print("[rank %d] %d files -> %d masks" % (rank, hi - lo, len(written)), flush=True)
+        for path, exc in errors:
+            print("[rank %d] %s: %s" % (rank, path, exc), file=sys.stderr, flush=True)
+        return 1 if errors else 0
     engine.set_persist(False)  # the driver never revisits an image's basis planes
     failed = 0
     for path in files[lo:hi]:

@@ -61,6 +61,9 @@ public:
     // `weight` is empty -- a largest weight >= minPeak, as 0 / 255 floats (cvs_contour_prune); returns the number kept.  countComponents:
     // the number of 8-connected components (cvs_label)
     int pruneContours(const Mat1f& mask, const Mat1f& weight, int minArea, float minPeak, Mat1f& out);
+    // the two in one labelling (extension, cvs_link): hysteresis(response, low, high) followed by pruneContours(that, response, minArea,
+    // minPeak), bit for bit, as 0 / 255 floats; minPeak = -INFINITY: no peak test
+    void linkContours(const Mat1f& response, float low, float high, int minArea, float minPeak, Mat1f& output);
     int countComponents(const Mat1f& mask);
 
 protected:

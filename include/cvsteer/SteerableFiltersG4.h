@@ -32,6 +32,8 @@ public:
     void steer(const std::vector<float>& thetas, std::vector<Mat1f>& g4, std::vector<Mat1f>& h4);
     // addition: contour components, as in SteerableFiltersG2 (cvs_contour_prune / cvs_label; they read the planes passed, not the object's state)
     int pruneContours(const Mat1f& mask, const Mat1f& weight, int minArea, float minPeak, Mat1f& out);
+    // addition: hysteresis and pruneContours(that, response, ...) in one labelling, as in SteerableFiltersG2 (cvs_link)
+    void linkContours(const Mat1f& response, float low, float high, int minArea, float minPeak, Mat1f& output);
     int countComponents(const Mat1f& mask);
 
 protected:

@@ -336,6 +336,52 @@ int cvs_contour_prune(cvs_handle h, int n, const cvs_plane* mask, const cvs_plan
 int cvs_contour_points(cvs_handle h, const cvs_plane* labels, int32_t* points, int capacity, int points_mem,
                        int* n_points);
 
+/* ---- EXTENSION beyond the reference: the contour chain on the batch axis -- cvs_link, cvs_nonmax_batch, cvs_contours_batch ----
+ * None of the three reads anything back: with device planes they queue a launch sequence that depends on the image size, the number of
+ * planes and how the planes lie in memory (one constant stride, or not) -- never on what the planes hold -- and return. */
+
+/* EXTENSION: hysteresis and prune in ONE labelling.  in: n >= 1 f32 planes of the handle's image size (typically the thinned maps of
+ * many frames; no upper limit on n).  Per plane, W = { pixels with v > low } (NaN is never in W); a component of W (8-connected) is
+ * KEPT iff its largest value is > high, its area is >= min_area, and its largest value is >= min_peak (IEEE float comparisons;
+ * min_peak = -INFINITY switches the last test off).  out: 255 on the pixels of kept components, 0 elsewhere; all CVS_DEPTH_U8 or all f32
+ * (255.0f / 0.0f), as in cvs_hysteresis.  kept_dev: NULL, or n ints in DEVICE memory that receive the number of components kept per
+ * plane; no count comes back to the host.
+ * Equivalence: byte for byte, and count for count, cvs_link(in, low, high, min_area, min_peak) is cvs_hysteresis(in, low, high)
+ * followed by cvs_contour_prune(mask = that, weight = in, min_area, min_peak): the mask hysteresis keeps is exactly the set of
+ * W-components that hold a strong pixel, and distinct W-components are never 8-adjacent, so relabelling that mask finds the same
+ * components with the same area and peak.  The output is a function of the inputs alone.
+ * Fixed, asynchronous, capturable: four launches per chain of planes (tiles, borders, statistics at the roots, emit), all planes of a
+ * chain in each; a chain holds as many planes as fit 1 GiB with their parent, area and peak planes (12 bytes per pixel; at least one), so the launch
+ * sequence depends on (rows, cols, n) and on whether the planes lie at one constant stride (an [N, H, W] block: addressed
+ * arithmetically) or not (a device table that launches fill from their arguments, 16 planes each).  No stream synchronisation and no
+ * copy to the host when all planes are device planes.  Under stream capture the call works provided the handle's scratch already has
+ * the size it needs (the same call, made once eagerly, sees to that); otherwise CVS_E_UNSUPPORTED, and the handle works on.  Host
+ * planes are staged on the device, at most eight planes per chain, synchronise, and are refused during capture.
+ * low > high, a NaN threshold, min_area < 0, NaN min_peak, n < 1, outputs of mixed depth, any overlap of an output with an input or
+ * another output: CVS_E_BADARG; a plane of another size than the handle's image: CVS_E_SIZE; no image size yet: CVS_E_STATE.  Nothing
+ * is written when an argument is rejected. */
+int cvs_link(cvs_handle h, int n, const cvs_plane* in, float low, float high, int min_area, float min_peak,
+             const cvs_plane* out, int32_t* kept_dev);
+
+/* EXTENSION: cvs_nonmax for `frames` frames of n_maps (1..3) maps each.  in / out: flat, frame-major arrays of frames * n_maps f32
+ * planes; theta: `frames` planes, or NULL = the CVS_PLANE_THETA state plane of frames 0 .. frames - 1 of the last cvs_pipeline_batch
+ * (CVS_E_STATE if the handle holds fewer frames, or no orientation state).  Every value is bit for bit that of cvs_nonmax on the same
+ * frame (the same kernel body).  ONE launch when the planes are on the device and the theta planes, and map k's in and out planes,
+ * each lie at a constant frame stride (an [F][K][H][W] block, the state blocks of a batch); otherwise one cvs_nonmax per frame.
+ * Errors as in cvs_nonmax; asynchronous on the handle's stream and capturable (device planes). */
+int cvs_nonmax_batch(cvs_handle h, int frames, int n_maps, const cvs_plane* theta, const cvs_plane* in, const cvs_plane* out);
+
+/* EXTENSION: thin, linked contours of n frames: cvs_pipeline_batch (state kept) -> the three maps of every frame in the handle's
+ * own scratch -> cvs_nonmax_batch(theta = NULL) -> cvs_link over the wanted planes.  outs: n * 3 planes, frame-major, {edges, dark,
+ * bright} per frame, all CVS_DEPTH_U8 or all f32; an entry with data == NULL is not wanted.  Every mask equals, byte for byte, what
+ * cvs_pipeline -> cvs_nonmax(theta = NULL) -> cvs_link(low, high, min_area, min_peak) writes for that frame alone on a handle of the
+ * same kind and options (G2, or G4 with CVS_OPT_G4_EXTENSIONS).  Afterwards the handle holds the state of all n frames, as after
+ * cvs_pipeline_batch.  CVS_OPT_PERSIST_STATE = 0: CVS_E_STATE (thinning needs the theta plane of every frame).  With device planes
+ * the call returns without synchronising; n = 1 is valid.  Threshold errors as in cvs_link; an output that overlaps the image of ANY
+ * frame, or another output: CVS_E_BADARG; frame errors as in cvs_pipeline_batch. */
+int cvs_contours_batch(cvs_handle h, const cvs_plane* images, int n, float low, float high, int min_area, float min_peak,
+                       const cvs_plane* outs);
+
 /* the whole caller sequence of test/test.cpp:85-90 / example/steer.cpp:86-90 for one image:
  * setup(FULL) -> steer(theta_dom, g2,h2,e,mag,phase) -> find*(mag|e, phase).
  * outs[8] = {g2, h2, e, magnitude, phase, edges, dark, bright}; any entry may be NULL.
