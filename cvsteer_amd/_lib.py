@@ -47,6 +47,13 @@ class Component(C.Structure):
                 ("first_x", C.c_int32), ("first_y", C.c_int32), ("peak_x", C.c_int32), ("peak_y", C.c_int32), ("peak", C.c_float)]
 
 
+class Chain(C.Structure):
+    """struct cvs_chain"""
+    _fields_ = [("start", C.c_int32), ("length", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+CHAIN_CLOSED, CHAIN_HEAD_JUNCTION, CHAIN_TAIL_JUNCTION = 1, 2, 4
+
 _PP = C.POINTER(Plane)
 _FP = C.POINTER(C.c_float)
 _IP = C.POINTER(C.c_int)
@@ -90,6 +97,7 @@ SIGNATURES = {
     "cvs_component_stats": (C.c_int, [C.c_void_p, _PP, C.c_int, _PP, C.c_void_p, C.c_int]),
     "cvs_contour_prune": (C.c_int, [C.c_void_p, C.c_int, _PP, _PP, C.c_int, C.c_float, _PP, _IP]),
     "cvs_contour_points": (C.c_int, [C.c_void_p, _PP, C.c_void_p, C.c_int, C.c_int, _IP]),
+    "cvs_contour_chains": (C.c_int, [C.c_void_p, _PP, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, _IP, _IP]),
     "cvs_link": (C.c_int, [C.c_void_p, C.c_int, _PP, C.c_float, C.c_float, C.c_int, C.c_float, _PP, C.c_void_p]),
     "cvs_nonmax_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _PP, _PP, _PP]),
     "cvs_contours_batch": (C.c_int, [C.c_void_p, _PP, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float, _PP]),

@@ -36,6 +36,7 @@ def _is_torch(a):
 
 
 KIND_G2, KIND_G4 = L.KIND_G2, L.KIND_G4
+CHAIN_CLOSED, CHAIN_HEAD_JUNCTION, CHAIN_TAIL_JUNCTION = L.CHAIN_CLOSED, L.CHAIN_HEAD_JUNCTION, L.CHAIN_TAIL_JUNCTION
 
 
 def alloc_planes(n, rows, cols, device=None):
@@ -643,6 +644,33 @@ class _CallerPipeline:
             if len(pts):
                 off[1:] = np.cumsum(np.bincount(pts[:, 2], minlength=top + 1)[1:])
         return pts, off
+
+    def contour_chains(self, mask):
+        """The linked contours of a mask as ordered chains of pixels, cut at junctions and free ends (cvs_contour_chains).  Returns
+        (points, chains): an (N, 2) int32 array of (x, y) and an (M, 4) int32 array of (start, length, flags, 0) -- chain c is
+        points[start:start + length], flags a sum of CHAIN_CLOSED, CHAIN_HEAD_JUNCTION, CHAIN_TAIL_JUNCTION.  Torch tensors on the
+        mask's device for a device mask, numpy arrays for a numpy mask.  The order of chains and points depends on the mask alone
+        (include/cvsteer_hip.h has the contract)."""
+        self._bind_stream(mask)
+        pm = _plane(mask)
+        n, m = C.c_int(0), C.c_int(0)
+        rc = lib().cvs_contour_chains(self._h, C.byref(pm), None, 0, None, 0, L.MEM_HOST, C.byref(n), C.byref(m))
+        if rc != L.E_SIZE:
+            self._check(rc, "cvs_contour_chains")
+        dev = _is_torch(mask) and mask.is_cuda
+        if dev:
+            pts = torch.empty((n.value, 2), dtype=torch.int32, device=mask.device)
+            chains = torch.empty((m.value, 4), dtype=torch.int32, device=mask.device)
+        else:
+            pts, chains = np.empty((n.value, 2), np.int32), np.empty((m.value, 4), np.int32)
+        if n.value:
+            pp = C.c_void_p(pts.data_ptr() if dev else pts.ctypes.data)
+            pc = C.c_void_p(chains.data_ptr() if dev else chains.ctypes.data)
+            self._check(lib().cvs_contour_chains(self._h, C.byref(pm), pp, n.value, pc, m.value, L.MEM_DEVICE if dev else L.MEM_HOST,
+                                                 C.byref(n), C.byref(m)), "cvs_contour_chains")
+        if _is_torch(mask) and not dev:
+            pts, chains = torch.from_numpy(pts), torch.from_numpy(chains)
+        return pts, chains
 
     def contours(self, image, low, high, min_area=0, min_peak=0.0):
         """Thin, linked contours of one image: pipeline(image) -> nonmax(edges, dark, bright) on the object's own theta ->

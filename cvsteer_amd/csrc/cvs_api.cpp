@@ -326,13 +326,14 @@ int cvs_destroy(cvs_handle h)
     (void)hipSetDevice(h->device);
     release_state(h);   // no drain: the block is parked with an event
     // staging memory exists only on handles that were given host planes, 8-bit conversions or irregular batches: those wait
-    if (h->arena || h->frame_tab || h->point_out || h->u8_scr || h->hy_scr || h->cc_scr || h->ct_scr) (void)hipStreamSynchronize(h->stream);
+    if (h->arena || h->frame_tab || h->point_out || h->u8_scr || h->hy_scr || h->cc_scr || h->ch_scr || h->ct_scr) (void)hipStreamSynchronize(h->stream);
     if (h->arena) (void)hipFree(h->arena);
     if (h->frame_tab) (void)hipFree(h->frame_tab);
     if (h->point_out) (void)hipFree(h->point_out);
     if (h->u8_scr) (void)hipFree(h->u8_scr);
     if (h->hy_scr) (void)hipFree(h->hy_scr);
     if (h->cc_scr) (void)hipFree(h->cc_scr);
+    if (h->ch_scr) (void)hipFree(h->ch_scr);
     if (h->ct_scr) (void)hipFree(h->ct_scr);
     if (h->ev_order) (void)hipEventDestroy(h->ev_order);
     for (hipEvent_t e : h->band_ev) (void)hipEventDestroy(e);

@@ -61,6 +61,10 @@ struct cvs_context {
     // partials, tables and point lists in staging; grown only, freed by cvs_destroy
     unsigned char* cc_scr = nullptr;
     size_t cc_scr_bytes = 0;
+    // contour chains (cvs_contour_chains): the arc arrays, sized by an arc count read back while the planes of that call still live in cc_scr
+    // (growing cc_scr would lose them), and the staging of host lists; grown only, freed by cvs_destroy
+    unsigned char* ch_scr = nullptr;
+    size_t ch_scr_bytes = 0;
     // contour batches (cvs_contours_batch): the three maps and the three thinned maps of every frame; grown only, freed by cvs_destroy
     float* ct_scr = nullptr;
     size_t ct_scr_elems = 0;

@@ -86,6 +86,28 @@ int count_components(cvs_handle h, const Mat1f& mask, int* n)
     return cvs_label(h, &pm, &pl, n);
 }
 
+// sized by a first call, then filled; the host loop here only re-packs the finished lists into vectors
+int trace_contours(cvs_handle h, const Mat1f& mask, std::vector<std::vector<Point> >& out, std::vector<int>* flags, int* n)
+{
+    cvs_plane pm = view(mask);
+    int np = 0, nc = 0;
+    int rc = cvs_contour_chains(h, &pm, 0, 0, 0, 0, CVS_MEM_HOST, &np, &nc);
+    if (rc != CVS_OK && rc != CVS_E_SIZE) return rc;
+    std::vector<int32_t> pts((size_t)np * 2);
+    std::vector<cvs_chain> tab((size_t)nc);
+    if (np > 0 && (rc = cvs_contour_chains(h, &pm, pts.data(), np, tab.data(), nc, CVS_MEM_HOST, &np, &nc)) != CVS_OK) return rc;
+    out.assign((size_t)nc, std::vector<Point>());
+    if (flags) flags->assign((size_t)nc, 0);
+    for (int c = 0; c < nc; ++c) {
+        const cvs_chain& t = tab[(size_t)c];
+        out[(size_t)c].reserve((size_t)t.length);
+        for (int k = 0; k < t.length; ++k) out[(size_t)c].push_back(Point(pts[2 * (size_t)(t.start + k)], pts[2 * (size_t)(t.start + k) + 1]));
+        if (flags) (*flags)[(size_t)c] = t.flags;
+    }
+    *n = nc;
+    return CVS_OK;
+}
+
 }  // namespace
 
 // --------------------------------------------------------------------------- base
@@ -330,6 +352,13 @@ int SteerableFiltersG2::countComponents(const Mat1f& mask)
     return n;
 }
 
+int SteerableFiltersG2::traceContours(const Mat1f& mask, std::vector<std::vector<Point> >& chains, std::vector<int>* flags)
+{
+    int n = 0;
+    check(trace_contours(m_handle, mask, chains, flags, &n), "cvs_contour_chains");
+    return n;
+}
+
 void SteerableFiltersG2::phaseWeights(const Mat1f& phase, Mat1f& lambda, float phi, bool signum, float k)
 {
     std::lock_guard<std::mutex> lock(g_static_mutex);
@@ -417,6 +446,13 @@ int SteerableFiltersG4::countComponents(const Mat1f& mask)
 {
     int n = 0;
     check(count_components(m_handle, mask, &n), "cvs_label");
+    return n;
+}
+
+int SteerableFiltersG4::traceContours(const Mat1f& mask, std::vector<std::vector<Point> >& chains, std::vector<int>* flags)
+{
+    int n = 0;
+    check(trace_contours(m_handle, mask, chains, flags, &n), "cvs_contour_chains");
     return n;
 }
 

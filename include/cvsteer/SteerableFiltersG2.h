@@ -65,6 +65,10 @@ public:
     // minPeak), bit for bit, as 0 / 255 floats; minPeak = -INFINITY: no peak test
     void linkContours(const Mat1f& response, float low, float high, int minArea, float minPeak, Mat1f& output);
     int countComponents(const Mat1f& mask);
+    // contour chains (extension, cvs_contour_chains): the linked contours of `mask` as ordered chains of pixels (x = column, y = row), cut
+    // at junctions and free ends, in the canonical order of include/cvsteer_hip.h; flags (optional): CVS_CHAIN_* per chain.  Returns the
+    // number of chains
+    int traceContours(const Mat1f& mask, std::vector<std::vector<Point> >& chains, std::vector<int>* flags = 0);
 
 protected:
     // the reference's protected members, same names (SteerableFiltersG2.h:62-66).  m_g1..m_h4 are the 7 tap vectors; the

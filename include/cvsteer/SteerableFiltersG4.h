@@ -35,6 +35,8 @@ public:
     // addition: hysteresis and pruneContours(that, response, ...) in one labelling, as in SteerableFiltersG2 (cvs_link)
     void linkContours(const Mat1f& response, float low, float high, int minArea, float minPeak, Mat1f& output);
     int countComponents(const Mat1f& mask);
+    // addition: ordered contour chains, as in SteerableFiltersG2 (cvs_contour_chains)
+    int traceContours(const Mat1f& mask, std::vector<std::vector<Point> >& chains, std::vector<int>* flags = 0);
 
 protected:
     // the reference's protected members, same names (SteerableFiltersG4.h:50-56): 11 tap vectors; the planes m_g4a..m_h4f

@@ -336,6 +336,47 @@ int cvs_contour_prune(cvs_handle h, int n, const cvs_plane* mask, const cvs_plan
 int cvs_contour_points(cvs_handle h, const cvs_plane* labels, int32_t* points, int capacity, int points_mem,
                        int* n_points);
 
+/* EXTENSION: the linked contours of `mask` as ORDERED chains of pixels, cut at junctions and free ends, in a canonical order that
+ * depends on the mask alone (integer arithmetic only: bit for bit).  With lin(p) = row * cols + col:
+ * LINKS.  Two foreground pixels are linked iff they are 4-adjacent, or they are diagonally adjacent and neither of the two pixels
+ * 4-adjacent to both is foreground (the redundant diagonal of a staircase corner is no link).  A pixel has at most 4 links, and the
+ * connected components of the links are the 8-connected components of the mask.
+ * NODES.  deg(p) = number of links of p; pixels with deg != 2 are nodes: 0 isolated, 1 a free end, >= 3 a junction.
+ * CHAINS.  Every link belongs to exactly one chain.  OPEN: a maximal sequence p0 .. pk, k >= 1, of consecutively linked pixels that
+ * uses no link twice, with p1 .. p(k-1) of degree 2 and p0, pk nodes (p0 == pk for a loop that leaves and re-enters a junction; a
+ * junction appears in each of its chains).  CLOSED: a component whose pixels all have degree 2 is one cycle, listed once from its
+ * pixel of smallest lin without repeating that pixel at the end, flag CVS_CHAIN_CLOSED.  ISOLATED: a pixel of degree 0 is a chain of
+ * one point.
+ * DIRECTION.  An open chain is listed in the direction whose first step (lin(p0), lin(p1)) is lexicographically smaller than the
+ * other direction's first step (lin(pk), lin(p(k-1))) -- the two are never equal; a closed chain goes from its smallest pixel
+ * towards the smaller of that pixel's two neighbours.
+ * ORDER.  Chains are sorted ascending by (lin(p0), lin(p1)), lin(p1) = -1 for an isolated pixel; points are stored chain after
+ * chain, so chains[c].start is the running sum of the lengths.  CVS_CHAIN_HEAD_JUNCTION iff deg(p0) >= 3, CVS_CHAIN_TAIL_JUNCTION iff
+ * deg(pk) >= 3; neither is ever set on a closed or isolated chain.
+ * points: room for point_capacity (x, y) int32 pairs; chains: room for chain_capacity entries; both in host or both in device memory
+ * (mem = CVS_MEM_HOST / CVS_MEM_DEVICE).  *n_points and *n_chains (both required) are always set; when either exceeds its capacity
+ * the call returns CVS_E_SIZE and writes no point and no chain (points = NULL, chains = NULL with both capacities 0 sizes the
+ * buffers).  Always n_points <= 4 * foreground pixels.  The counts follow from degrees and components alone -- open chains = half
+ * the sum of the degrees of the nodes, closed chains = components without a node, points = links + open chains + isolated pixels --
+ * so the sizing call orders nothing.  A NULL array with a capacity > 0, or a negative capacity: CVS_E_BADARG.
+ * Foreground as in cvs_label; f32 or CVS_DEPTH_U8 masks, host or device, pitched or dense.  Like the component calls: synchronises
+ * the handle's stream, CVS_E_UNSUPPORTED while it is being captured, CVS_E_STATE before the first setup, CVS_E_SIZE for a plane of
+ * another size or for rows * cols > 2^28; nothing is written when an argument is rejected.  The launch sequence depends on the image
+ * size and on ceil(log2) of the number of directed links (read back), never on the length or winding of a contour.  Device memory:
+ * 10 bytes per pixel and 24 bytes per directed link of handle scratch. */
+typedef struct cvs_chain {   /* 16 bytes */
+    int32_t start;           /* index of the chain's first point in `points` */
+    int32_t length;          /* number of points, >= 1 */
+    int32_t flags;           /* CVS_CHAIN_CLOSED = 1, CVS_CHAIN_HEAD_JUNCTION = 2, CVS_CHAIN_TAIL_JUNCTION = 4 */
+    int32_t reserved;        /* 0 */
+} cvs_chain;
+enum { CVS_CHAIN_CLOSED = 1, CVS_CHAIN_HEAD_JUNCTION = 2, CVS_CHAIN_TAIL_JUNCTION = 4 };
+int cvs_contour_chains(cvs_handle h, const cvs_plane* mask,
+                       int32_t* points, int point_capacity,     /* (x, y) int32 pairs */
+                       cvs_chain* chains, int chain_capacity,
+                       int mem,                                 /* CVS_MEM_HOST / CVS_MEM_DEVICE, both arrays */
+                       int* n_points, int* n_chains);           /* both required, always set */
+
 /* ---- EXTENSION beyond the reference: the contour chain on the batch axis -- cvs_link, cvs_nonmax_batch, cvs_contours_batch ----
  * None of the three reads anything back: with device planes they queue a launch sequence that depends on the image size, the number of
  * planes and how the planes lie in memory (one constant stride, or not) -- never on what the planes hold -- and return. */
