@@ -98,6 +98,8 @@ SIGNATURES = {
     "cvs_contour_prune": (C.c_int, [C.c_void_p, C.c_int, _PP, _PP, C.c_int, C.c_float, _PP, _IP]),
     "cvs_contour_points": (C.c_int, [C.c_void_p, _PP, C.c_void_p, C.c_int, C.c_int, _IP]),
     "cvs_contour_chains": (C.c_int, [C.c_void_p, _PP, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, _IP, _IP]),
+    "cvs_chain_polylines": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p,
+                                      C.c_void_p, C.c_int, _IP]),
     "cvs_link": (C.c_int, [C.c_void_p, C.c_int, _PP, C.c_float, C.c_float, C.c_int, C.c_float, _PP, C.c_void_p]),
     "cvs_nonmax_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _PP, _PP, _PP]),
     "cvs_contours_batch": (C.c_int, [C.c_void_p, _PP, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float, _PP]),

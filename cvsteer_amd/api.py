@@ -672,6 +672,48 @@ class _CallerPipeline:
             pts, chains = torch.from_numpy(pts), torch.from_numpy(chains)
         return pts, chains
 
+    def chain_polylines(self, points, chains, eps, return_index=False):
+        """Simplify every chain to a polyline (cvs_chain_polylines): Ramer-Douglas-Peucker with tolerance eps (pixels; inf keeps the
+        end points only) on all chains at once.  points (N, 2) int32 and chains (M, 4) int32 as contour_chains returns them.  Returns
+        (vertices (V, 2) int32, polylines (M, 4) int32 of (start, length, flags, 0)[, index (V,) int32: vertex k is points[index[k]]]).
+        Torch CUDA tensors take the device path and give tensors on their device; numpy arrays take the host path (torch CPU tensors
+        too, and come back as such).  Which points are kept depends on the inputs alone (include/cvsteer_hip.h has the contract)."""
+        dev = _is_torch(points) and points.is_cuda
+        if dev != (_is_torch(chains) and chains.is_cuda):
+            raise ValueError("points and chains: both on the device or both on the host")
+        back = _is_torch(points) and not dev
+        if dev:
+            points, chains = points.to(torch.int32).contiguous(), chains.to(torch.int32).contiguous()
+        else:
+            points = np.ascontiguousarray(points.numpy() if _is_torch(points) else points, np.int32)
+            chains = np.ascontiguousarray(chains.numpy() if _is_torch(chains) else chains, np.int32)
+        if points.ndim != 2 or points.shape[1] != 2 or chains.ndim != 2 or chains.shape[1] != 4:
+            raise ValueError("points must be (N, 2) and chains (M, 4)")
+        n, m = int(points.shape[0]), int(chains.shape[0])
+        if dev:
+            self._bind_stream(points)
+            vtx = torch.empty((n, 2), dtype=torch.int32, device=points.device)
+            idx = torch.empty((n,), dtype=torch.int32, device=points.device) if return_index else None
+            tab = torch.empty((m, 4), dtype=torch.int32, device=points.device)
+            ptr = lambda t: None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())
+        else:
+            vtx, idx, tab = np.empty((n, 2), np.int32), (np.empty((n,), np.int32) if return_index else None), np.empty((m, 4), np.int32)
+            ptr = lambda t: None if t is None or t.size == 0 else C.c_void_p(t.ctypes.data)
+        v = C.c_int(0)
+        self._check(lib().cvs_chain_polylines(self._h, ptr(points), n, ptr(chains), m, float(eps), ptr(vtx), n, ptr(idx), ptr(tab),
+                                              L.MEM_DEVICE if dev else L.MEM_HOST, C.byref(v)), "cvs_chain_polylines")
+        vtx = vtx[:v.value]
+        idx = None if idx is None else idx[:v.value]
+        if back:
+            vtx, tab, idx = torch.from_numpy(vtx), torch.from_numpy(tab), (None if idx is None else torch.from_numpy(idx))
+        return (vtx, tab, idx) if return_index else (vtx, tab)
+
+    def contour_polylines(self, mask, eps, return_index=False):
+        """contour_chains(mask) followed by chain_polylines(..., eps): the linked contours of a mask as polylines.  With
+        return_index=True the index refers to the points of contour_chains(mask)."""
+        points, chains = self.contour_chains(mask)
+        return self.chain_polylines(points, chains, eps, return_index=return_index)
+
     def contours(self, image, low, high, min_area=0, min_peak=0.0):
         """Thin, linked contours of one image: pipeline(image) -> nonmax(edges, dark, bright) on the object's own theta ->
         hysteresis(low, high).  Returns three uint8 masks (edges, dark lines, bright lines).  min_area > 0 or min_peak > 0: the

@@ -108,6 +108,41 @@ int trace_contours(cvs_handle h, const Mat1f& mask, std::vector<std::vector<Poin
     return CVS_OK;
 }
 
+// the chains packed into one point list and a table, one call, the polylines unpacked again: no arithmetic on the host
+int approx_contours(cvs_handle h, const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags, float eps,
+                    std::vector<std::vector<Point> >& out, int* n)
+{
+    if (flags && flags->size() != chains.size()) return CVS_E_BADARG;
+    size_t np = 0;
+    for (size_t c = 0; c < chains.size(); ++c) np += chains[c].size();
+    if (np > (size_t)1 << 30) return CVS_E_SIZE;
+    std::vector<int32_t> pts(np * 2), vtx(np * 2);
+    std::vector<cvs_chain> tab(chains.size()), pol(chains.size());
+    size_t at = 0;
+    for (size_t c = 0; c < chains.size(); ++c) {
+        tab[c].start = (int32_t)at;
+        tab[c].length = (int32_t)chains[c].size();
+        tab[c].flags = flags ? (*flags)[c] : 0;
+        tab[c].reserved = 0;
+        for (size_t k = 0; k < chains[c].size(); ++k, ++at) {
+            pts[2 * at] = chains[c][k].x;
+            pts[2 * at + 1] = chains[c][k].y;
+        }
+    }
+    int nv = 0;
+    const int rc = cvs_chain_polylines(h, pts.data(), (int)np, tab.data(), (int)chains.size(), eps, vtx.data(), (int)np, 0, pol.data(),
+                                       CVS_MEM_HOST, &nv);
+    if (rc != CVS_OK) return rc;
+    out.assign(chains.size(), std::vector<Point>());
+    for (size_t c = 0; c < chains.size(); ++c) {
+        const cvs_chain& t = pol[c];
+        out[c].reserve((size_t)t.length);
+        for (int k = 0; k < t.length; ++k) out[c].push_back(Point(vtx[2 * (size_t)(t.start + k)], vtx[2 * (size_t)(t.start + k) + 1]));
+    }
+    *n = nv;
+    return CVS_OK;
+}
+
 }  // namespace
 
 // --------------------------------------------------------------------------- base
@@ -359,6 +394,14 @@ int SteerableFiltersG2::traceContours(const Mat1f& mask, std::vector<std::vector
     return n;
 }
 
+int SteerableFiltersG2::approxContours(const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags, float epsilon,
+                                       std::vector<std::vector<Point> >& polylines)
+{
+    int n = 0;
+    check(approx_contours(m_handle, chains, flags, epsilon, polylines, &n), "cvs_chain_polylines");
+    return n;
+}
+
 void SteerableFiltersG2::phaseWeights(const Mat1f& phase, Mat1f& lambda, float phi, bool signum, float k)
 {
     std::lock_guard<std::mutex> lock(g_static_mutex);
@@ -453,6 +496,14 @@ int SteerableFiltersG4::traceContours(const Mat1f& mask, std::vector<std::vector
 {
     int n = 0;
     check(trace_contours(m_handle, mask, chains, flags, &n), "cvs_contour_chains");
+    return n;
+}
+
+int SteerableFiltersG4::approxContours(const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags, float epsilon,
+                                       std::vector<std::vector<Point> >& polylines)
+{
+    int n = 0;
+    check(approx_contours(m_handle, chains, flags, epsilon, polylines, &n), "cvs_chain_polylines");
     return n;
 }
 

@@ -69,6 +69,11 @@ public:
     // at junctions and free ends, in the canonical order of include/cvsteer_hip.h; flags (optional): CVS_CHAIN_* per chain.  Returns the
     // number of chains
     int traceContours(const Mat1f& mask, std::vector<std::vector<Point> >& chains, std::vector<int>* flags = 0);
+    // contour polylines (extension, cvs_chain_polylines): Ramer-Douglas-Peucker simplification of all chains at once with tolerance
+    // `epsilon` (pixels), by the split rule of include/cvsteer_hip.h; flags: what traceContours returned (a chain with CVS_CHAIN_CLOSED is
+    // treated as a cycle), 0 = all chains open.  polylines[c] = the kept points of chains[c] in order.  Returns the number of vertices
+    int approxContours(const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags, float epsilon,
+                       std::vector<std::vector<Point> >& polylines);
 
 protected:
     // the reference's protected members, same names (SteerableFiltersG2.h:62-66).  m_g1..m_h4 are the 7 tap vectors; the

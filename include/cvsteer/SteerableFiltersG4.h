@@ -37,6 +37,9 @@ public:
     int countComponents(const Mat1f& mask);
     // addition: ordered contour chains, as in SteerableFiltersG2 (cvs_contour_chains)
     int traceContours(const Mat1f& mask, std::vector<std::vector<Point> >& chains, std::vector<int>* flags = 0);
+    // addition: polylines of the chains, as in SteerableFiltersG2 (cvs_chain_polylines)
+    int approxContours(const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags, float epsilon,
+                       std::vector<std::vector<Point> >& polylines);
 
 protected:
     // the reference's protected members, same names (SteerableFiltersG4.h:50-56): 11 tap vectors; the planes m_g4a..m_h4f

@@ -377,6 +377,43 @@ int cvs_contour_chains(cvs_handle h, const cvs_plane* mask,
                        int mem,                                 /* CVS_MEM_HOST / CVS_MEM_DEVICE, both arrays */
                        int* n_points, int* n_chains);           /* both required, always set */
 
+/* EXTENSION: Ramer-Douglas-Peucker simplification of all chains of a chain table at once: every chain becomes the polyline of its
+ * KEPT points.  Needs no image size (any handle, before or after a setup): the handle supplies the stream and the scratch.
+ * VIRTUAL LIST.  For chain c with points P[0 .. L), Q = P; for a chain with CVS_CHAIN_CLOSED, Q = P followed by P[0] again, n = L + 1
+ * (the repeated point is virtual and never emitted).  Q[0] and Q[n-1] are kept.  L <= 2: every point is kept.
+ * SPLIT RULE.  A segment (lo, hi) with hi - lo >= 2, a = Q[lo], b = Q[hi]: for every interior i,
+ *   v(i) = |(bx-ax)*(Q[i].y-ay) - (by-ay)*(Q[i].x-ax)| if a != b, else v(i) = (Q[i].x-ax)^2 + (Q[i].y-ay)^2,
+ * both int64 and exact for |x|, |y| < 2^28.  m = the SMALLEST i with the largest v.  The test, in IEEE double with one rounding per
+ * operation, is num > e2 * den with e2 = (double)eps * (double)eps (exact); for a != b: num = (double)v(m) * (double)v(m) and
+ * den = (double)(dx*dx + dy*dy), the sum in int64; for a == b: num = (double)v(m), den = 1.0.  If it holds, Q[m] is kept and (lo, m),
+ * (m, hi) are split in turn; otherwise nothing between lo and hi is kept.  The a == b rule is what serves closed chains and open loops
+ * that leave and re-enter a junction (p0 == pk).  The kept set does not depend on the order in which segments are visited, and the
+ * result is a function of the inputs alone, bit for bit.
+ * OUTPUT.  Polyline c = the kept points of chain c in chain order, polylines[c] = (start, length, flags of chains[c], 0) with start
+ * the running sum of the lengths; vertices: (x, y) pairs; index (may be NULL): index[k] = position in `points` of vertex k.  Always
+ * n_vertices <= n_points, so a caller may allocate n_points vertices and call once.
+ * points, chains, vertices, index and polylines are all in host or all in device memory (mem).  *n_vertices (required) is set by every
+ * call that gets as far as counting (CVS_OK and CVS_E_SIZE): when it exceeds vertex_capacity the call returns CVS_E_SIZE and writes no
+ * vertex, no index and no table entry (vertices = NULL with capacity 0 is the sizing call; polylines may be NULL then and when
+ * n_chains == 0).  CVS_E_BADARG, nothing written and *n_vertices untouched: eps NaN or negative (+INFINITY is valid and keeps only the
+ * end points), a negative count or capacity, a required array missing, mem invalid, a pointer not aligned to 4 bytes, and a HOST table
+ * with an entry that violates start >= 0, length >= 1, start + length <= n_points.  A DEVICE table is trusted for its meaning, but the
+ * kernels treat an entry that fails those three conditions as an empty chain (length 0 in the output), so no load or store ever
+ * leaves the arrays; coordinates are never used as addresses.  Coordinates outside +-2^28 give unspecified vertices and no fault;
+ * n_points > 2^30: CVS_E_SIZE.  Reads one count back: synchronises the handle's stream, CVS_E_UNSUPPORTED while it is being captured.
+ * The launch sequence (seven launches) depends on (n_points, n_chains) alone, never on the length or winding of a contour: chains of
+ * up to 256 points are carried by one wave each, longer ones by one 256-lane workgroup each.  Device memory: 1 byte per point and
+ * 4 bytes per chain of handle scratch (plus 4 bytes per 1024 chains, plus the staged arrays of a host call). */
+int cvs_chain_polylines(cvs_handle h,
+                        const int32_t* points, int n_points,        /* (x, y) pairs, as cvs_contour_chains writes them */
+                        const cvs_chain* chains, int n_chains,      /* chain c = points[start .. start + length) */
+                        float eps,
+                        int32_t* vertices, int vertex_capacity,     /* (x, y) pairs of the kept points */
+                        int32_t* index,                             /* NULL, or vertex_capacity ints: position of each vertex in `points` */
+                        cvs_chain* polylines,                       /* NULL only when n_chains == 0 or sizing; else n_chains entries */
+                        int mem,                                    /* CVS_MEM_HOST / CVS_MEM_DEVICE: all five arrays */
+                        int* n_vertices);                           /* required, always set */
+
 /* ---- EXTENSION beyond the reference: the contour chain on the batch axis -- cvs_link, cvs_nonmax_batch, cvs_contours_batch ----
  * None of the three reads anything back: with device planes they queue a launch sequence that depends on the image size, the number of
  * planes and how the planes lie in memory (one constant stride, or not) -- never on what the planes hold -- and return. */
