@@ -93,7 +93,8 @@ def test_non_contiguous_input_step(cv, ora):
 
 # ----------------------------------------------------------------------------- orientation
 def test_orientation_same_basis_in(cv, ora):
-    """C1..C3 / strength / theta from the GPU's own basis planes: same op order as the oracle"""
+    """C1..C3 / strength / theta from the GPU's own basis planes: same op order as the oracle
+    (the oracle-free float64 check of every launch, on every pixel: tests/test_gpu_orientation.py)"""
     for img in (rand_image(64, 96, seed=3), smooth_image(90, 130)):
         f = cv.SteerableFiltersG2(img, 4, 0.67)
         b = _basis_stack(f, 7)
@@ -1032,7 +1033,8 @@ def test_random_shapes_fuzz(cv, ora):
 
 
 def test_g4_extension_orientation_and_full_steer(cv, ora):
-    """opt-in extension beyond the reference: G4 C1..C3 / theta / strength, steer(full), mag/phase"""
+    """opt-in extension beyond the reference: G4 C1..C3 / theta / strength, steer(full), mag/phase
+    (the table-free float64 check of the G4 orientation, on every pixel: tests/test_gpu_orientation.py)"""
     img = smooth_image(70, 110) + 0.05 * rand_image(70, 110, seed=77)
     f = cv.SteerableFiltersG4(img, extensions=True)
     b = np.stack([f.basis(p) for p in range(11)])
