@@ -113,6 +113,10 @@ def _plane(a):
     return Plane(a.ctypes.data, a.shape[0], a.shape[1], step, L.MEM_HOST)
 
 
+def _planes(seq):
+    return (Plane * len(seq))(*[_plane(x) for x in seq])
+
+
 def _as_input(a):
     """the reference converts any Mat to Mat1f unscaled (Mat1f(const Mat&)); do the same on the host side"""
     if _is_torch(a):
@@ -488,7 +492,7 @@ class _CallerPipeline:
             else:
                 out = np.empty((n, len(sel)) + shape, np.uint8 if u8 else np.float32)
         self._bind_stream(planes[0], out[0][0])
-        imgs = (Plane * n)(*[_plane(p) for p in planes])
+        imgs = _planes(planes)
         outs = (Plane * (n * 8))()  # zero-initialised: data == NULL means "not requested"
         for i in range(n):
             for j, k in enumerate(sel):
@@ -517,7 +521,7 @@ class _CallerPipeline:
             raise ValueError("out: one plane per map")
         self._bind_stream(*ms, *outs, *([] if theta is None else [theta]))
         n = len(ms)
-        pin, pout = (Plane * n)(*[_plane(m) for m in ms]), (Plane * n)(*[_plane(o) for o in outs])
+        pin, pout = _planes(ms), _planes(outs)
         pt = None if theta is None else C.byref(_plane(theta))
         self._check(lib().cvs_nonmax(self._h, pt, n, pin, pout), "cvs_nonmax")
         return outs[0] if single else tuple(outs)
@@ -529,20 +533,10 @@ class _CallerPipeline:
         self._caller_check("cvs_hysteresis")
         single, ms = self._plane_list(maps, 1 << 30, "hysteresis")
         u8 = self._u8_dtype(dtype)
-        if out is None:
-            outs = []
-            for m in ms:
-                if _is_torch(m):
-                    outs.append(torch.empty(tuple(m.shape), dtype=torch.uint8 if u8 else torch.float32, device=m.device))
-                else:
-                    outs.append(np.empty(m.shape, np.uint8 if u8 else np.float32))
-        else:
-            outs = [out] if single else list(out)
-        if len(outs) != len(ms):
-            raise ValueError("out: one plane per map")
+        outs = self._mask_outs(ms, u8, out, single, "map")
         self._bind_stream(*ms, *outs)
         n = len(ms)
-        pin, pout = (Plane * n)(*[_plane(m) for m in ms]), (Plane * n)(*[_plane(o) for o in outs])
+        pin, pout = _planes(ms), _planes(outs)
         passes = C.c_int(0)
         self._check(lib().cvs_hysteresis(self._h, n, pin, float(low), float(high), pout, C.byref(passes)), "cvs_hysteresis")
         res = outs[0] if single else tuple(outs)
@@ -553,15 +547,25 @@ class _CallerPipeline:
                                 ("first_y", "<i4"), ("peak_x", "<i4"), ("peak_y", "<i4"), ("peak", "<f4")])
 
     @staticmethod
-    def _new_typed_like(a, dtype_np, dtype_t):
+    def _new_typed_like(a, dtype_np):
         if _is_torch(a):
-            return torch.empty(tuple(a.shape), dtype=dtype_t, device=a.device)
+            return torch.empty(tuple(a.shape), dtype=getattr(torch, np.dtype(dtype_np).name), device=a.device)
         return np.empty(a.shape, dtype_np)
+
+    def _mask_outs(self, ms, u8, out, single, what):
+        """The outputs of hysteresis / prune / link: `out` as given, or a new plane like each input, bytes or f32."""
+        if out is None:
+            outs = [self._new_typed_like(m, np.uint8 if u8 else np.float32) for m in ms]
+        else:
+            outs = [out] if single else list(out)
+        if len(outs) != len(ms):
+            raise ValueError("out: one plane per %s" % what)
+        return outs
 
     def label(self, mask, out=None):
         """8-connected components of a mask (cvs_label): float32 (foreground: > 0) or uint8 (non-zero).  Returns (labels, count): an
         int32 plane like `mask`, 0 for background and 1 .. count in raster order of each component's first pixel."""
-        labels = self._new_typed_like(mask, np.int32, torch.int32 if torch is not None else None) if out is None else out
+        labels = self._new_typed_like(mask, np.int32) if out is None else out
         self._bind_stream(mask, labels)
         pm, pl = _plane(mask), _plane(labels)
         count = C.c_int(0)
@@ -589,17 +593,11 @@ class _CallerPipeline:
         if ws is not None and len(ws) != len(ms):
             raise ValueError("weight: one plane per mask")
         u8 = self._u8_dtype(dtype)
-        if out is None:
-            outs = [self._new_typed_like(m, np.uint8 if u8 else np.float32, (torch.uint8 if u8 else torch.float32) if torch is not None else None)
-                    for m in ms]
-        else:
-            outs = [out] if single else list(out)
-        if len(outs) != len(ms):
-            raise ValueError("out: one plane per mask")
+        outs = self._mask_outs(ms, u8, out, single, "mask")
         self._bind_stream(*ms, *outs, *(ws or []))
         n = len(ms)
-        pin, pout = (Plane * n)(*[_plane(m) for m in ms]), (Plane * n)(*[_plane(o) for o in outs])
-        pw = None if ws is None else (Plane * n)(*[_plane(w) for w in ws])
+        pin, pout = _planes(ms), _planes(outs)
+        pw = None if ws is None else _planes(ws)
         kept = (C.c_int * n)()
         self._check(lib().cvs_contour_prune(self._h, n, pin, pw, int(min_area), float(min_peak), pout, kept), "cvs_contour_prune")
         res = outs[0] if single else tuple(outs)
@@ -768,16 +766,10 @@ class _CallerPipeline:
             keep = (maps, out)
         else:
             single, ms = self._plane_list(maps, 1 << 30, "link")
-            if out is None:
-                outs = [self._new_typed_like(m, np.uint8 if u8 else np.float32, (torch.uint8 if u8 else torch.float32) if torch is not None else None)
-                        for m in ms]
-            else:
-                outs = [out] if single else list(out)
-            if len(outs) != len(ms):
-                raise ValueError("out: one plane per map")
+            outs = self._mask_outs(ms, u8, out, single, "map")
             self._bind_stream(*ms, *outs)
             n = len(ms)
-            pin, pout = (Plane * n)(*[_plane(m) for m in ms]), (Plane * n)(*[_plane(o) for o in outs])
+            pin, pout = _planes(ms), _planes(outs)
             res = outs[0] if single else tuple(outs)
             keep = (ms, outs)
         kept = None
@@ -817,8 +809,7 @@ class _CallerPipeline:
             if len(rows_out) != frames or any(len(fr) != k for fr in rows_out):
                 raise ValueError("out: one plane per map")
             flat_in, flat_out = [m for fr in rows_in for m in fr], [o for fr in rows_out for o in fr]
-            pin = (Plane * (frames * k))(*[_plane(m) for m in flat_in])
-            pout = (Plane * (frames * k))(*[_plane(o) for o in flat_out])
+            pin, pout = _planes(flat_in), _planes(flat_out)
             res = out if out is not None else [tuple(fr) for fr in rows_out]
         pt, ths = None, []
         if theta is not None:
@@ -830,7 +821,7 @@ class _CallerPipeline:
                 ths = list(theta)
                 if len(ths) != frames:
                     raise ValueError("theta: one plane per frame")
-                pt = (Plane * frames)(*[_plane(t) for t in ths])
+                pt = _planes(ths)
         self._bind_stream(*flat_in, *flat_out, *ths)
         self._check(lib().cvs_nonmax_batch(self._h, frames, k, pt, pin, pout), "cvs_nonmax_batch")
         self._nms_keepalive = (flat_in, flat_out, ths)
@@ -861,8 +852,7 @@ class _CallerPipeline:
                 out = torch.empty(shape, dtype=torch.uint8, device=planes[0].device)
             else:
                 out = np.empty(shape, np.uint8)
-            pim = (Plane * n)(*[_plane(p) for p in planes])
-            pout = (Plane * (3 * n))(*[_plane(out[i][k]) for i in range(n) for k in range(3)])
+            pim, pout = _planes(planes), _planes([out[i][k] for i in range(n) for k in range(3)])
         self._bind_stream(*planes, out)
         self._check(lib().cvs_contours_batch(self._h, pim, n, float(low), float(high), int(min_area), float(min_peak), pout),
                     "cvs_contours_batch")

@@ -1,6 +1,6 @@
 // cvs_api.cpp -- the C ABI of libcvsteer_hip.so (declared in include/cvsteer_hip.h) but for the caller pipeline (cvs_pipeline.cpp)
 // and the multi-GPU batch layer (cvs_batch.cpp): handles and options, the setup calls and do_setup behind them, state access, steering,
-// the per-pixel stages and contour thinning.
+// and the per-pixel stages.
 //
 // Argument checks, device-state ownership, host<->device staging when a caller hands over host planes, and kernel dispatch.  All
 // arithmetic on the hot path is in the HIP kernels; the only host arithmetic is what the reference also does on the host before it
@@ -13,7 +13,6 @@
 #include <new>
 #include <vector>
 
-#include "cvs_contour.h"
 #include "cvs_context.h"
 #include "cvs_layout.h"
 
@@ -191,19 +190,19 @@ int cvs::do_setup(cvs_handle h, const SetupReq& rq)
     return finish(c);
 }
 
-namespace {
-
-void basis_inputs(cvs_handle h, PointArgs& a)
-{
-    for (int p = 0; p < h->nb; ++p) a.in[p] = state_ref(h, p);
-}
-
-int need_state(cvs_handle h, bool orient)
+int cvs::need_state(cvs_handle h, bool orient)
 {
     if (!h) return CVS_E_BADARG;
     if (!h->have_basis) return fail(h, CVS_E_STATE, "no setup yet");
     if (orient && !h->have_orient) return fail(h, CVS_E_STATE, "orientation state not computed (setup without CVS_SETUP_ORIENT)");
     return CVS_OK;
+}
+
+namespace {
+
+void basis_inputs(cvs_handle h, PointArgs& a)
+{
+    for (int p = 0; p < h->nb; ++p) a.in[p] = state_ref(h, p);
 }
 
 int steer_common(cvs_handle h, bool map, float theta, const cvs_plane* theta_map, const cvs_plane* g, const cvs_plane* hq,
@@ -828,244 +827,6 @@ int cvs_find(cvs_handle h, const cvs_plane* e, const cvs_plane* phase, const cvs
     a.nt_stores = use_nt_stores(h, (size_t)a.rows * a.cols);
     HIP_TRY(h, launch_point(OP_FIND, a, h->stream));
     return finish(c);
-}
-
-// ---- contour thinning (extension; cvs_kernels_contour.hip) ----
-
-// every output against every input and every other output: any shared byte is an error (unlike check_point_overlaps, an output may
-// not BE an input either -- both kernels read the neighbours of the pixel they write)
-static int contour_overlaps(cvs_handle h, const std::vector<const cvs_plane*>& ins, const cvs_plane* outs, int n)
-{
-    std::vector<const cvs_plane*> o;
-    for (int k = 0; k < n; ++k) o.push_back(&outs[k]);
-    for (size_t k = 0; k < o.size(); ++k) {
-        for (const cvs_plane* i : ins)
-            if (planes_overlap(o[k], i)) return fail(h, CVS_E_BADARG, "an output plane overlaps an input plane");
-        for (size_t j = k + 1; j < o.size(); ++j)
-            if (planes_overlap(o[k], o[j])) return fail(h, CVS_E_BADARG, "two output planes overlap each other");
-    }
-    return CVS_OK;
-}
-
-int cvs_nonmax(cvs_handle h, const cvs_plane* theta, int n, const cvs_plane* in, const cvs_plane* out)
-{
-    if (!h) return CVS_E_BADARG;
-    if (n < 1 || n > kNmsMax || !in || !out) return fail(h, CVS_E_BADARG, "1..3 maps, in and out are required");
-    int rc;
-    if (!theta && (rc = need_state(h, true))) return rc;
-    if (h->rows <= 0) return fail(h, CVS_E_STATE, "no setup yet: the handle has no image size");
-    if (theta && ((rc = check_plane(h, theta, "theta")) || (rc = check_same(h, theta, h->rows, h->cols)))) return rc;
-    for (int k = 0; k < n; ++k) {
-        if ((rc = check_plane(h, &in[k], "in")) || (rc = check_same(h, &in[k], h->rows, h->cols))) return rc;
-        if ((rc = check_plane(h, &out[k], "out")) || (rc = check_same(h, &out[k], h->rows, h->cols))) return rc;
-    }
-    // theta == NULL: the handle's own theta plane of the selected frame -- an output must not overlap that either
-    cvs_plane own{};
-    if (!theta) {
-        const PlaneRef r = state_ref(h, h->nb + 3);
-        own.data = r.p;
-        own.rows = h->rows;
-        own.cols = h->cols;
-        own.step = r.pitch * sizeof(float);
-        own.mem = CVS_MEM_DEVICE;
-    }
-    std::vector<const cvs_plane*> ins = {theta ? theta : &own};
-    for (int k = 0; k < n; ++k) ins.push_back(&in[k]);
-    if ((rc = contour_overlaps(h, ins, out, n))) return rc;
-
-    const cvs_plane* pin[kNmsMax] = {nullptr, nullptr, nullptr};
-    const cvs_plane* pout[kNmsMax] = {nullptr, nullptr, nullptr};
-    for (int k = 0; k < n; ++k) {
-        pin[k] = &in[k];
-        pout[k] = &out[k];
-    }
-    Call c;
-    if ((rc = begin(h, c, {theta, pin[0], pin[1], pin[2], pout[0], pout[1], pout[2]}))) return rc;
-    NmsArgs a{};
-    a.rows = h->rows;
-    a.cols = h->cols;
-    a.n = n;
-    if (theta) {
-        if ((rc = in_ref(c, theta, a.theta))) return rc;
-    } else {
-        a.theta = state_ref(h, h->nb + 3);
-    }
-    for (int k = 0; k < n; ++k)
-        if ((rc = in_ref(c, pin[k], a.in[k])) || (rc = out_ref(c, pout[k], a.out[k]))) return rc;
-    a.nt_stores = use_nt_stores(h, (size_t)a.rows * a.cols);
-    HIP_TRY(h, launch_nonmax(a, h->stream));
-    return finish(c);
-}
-
-int cvs_nonmax_batch(cvs_handle h, int frames, int n_maps, const cvs_plane* theta, const cvs_plane* in, const cvs_plane* out)
-{
-    if (!h) return CVS_E_BADARG;
-    if (frames < 1 || n_maps < 1 || n_maps > kNmsMax || !in || !out) return fail(h, CVS_E_BADARG, "frames >= 1, 1..3 maps, in and out are required");
-    int rc;
-    if (!theta && (rc = need_state(h, true))) return rc;
-    if (h->rows <= 0) return fail(h, CVS_E_STATE, "no setup yet: the handle has no image size");
-    if (!theta && frames > h->num_frames) return fail(h, CVS_E_STATE, "the handle holds the state of fewer frames");
-    const int rows = h->rows, cols = h->cols;
-    const size_t np = (size_t)frames * n_maps;
-    for (int f = 0; theta && f < frames; ++f)
-        if ((rc = check_plane(h, &theta[f], "theta")) || (rc = check_same(h, &theta[f], rows, cols))) return rc;
-    for (size_t k = 0; k < np; ++k) {
-        if ((rc = check_plane(h, &in[k], "in")) || (rc = check_same(h, &in[k], rows, cols))) return rc;
-        if ((rc = check_plane(h, &out[k], "out")) || (rc = check_same(h, &out[k], rows, cols))) return rc;
-    }
-    // theta == NULL: the theta state planes of frames 0 .. frames - 1 -- an output must not overlap those either
-    std::vector<cvs_plane> own;
-    if (!theta) {
-        const PlaneRef r = state_ref(h, h->nb + 3);   // of the selected frame; frame f lies (f - cur_frame) frame strides from it
-        for (int f = 0; f < frames; ++f) {
-            cvs_plane p{};
-            p.data = r.p + ((ptrdiff_t)f - h->cur_frame) * (ptrdiff_t)h->frame_stride;
-            p.rows = rows;
-            p.cols = cols;
-            p.step = r.pitch * sizeof(float);
-            p.mem = CVS_MEM_DEVICE;
-            own.push_back(p);
-        }
-        theta = own.data();
-    }
-    std::vector<const cvs_plane*> ins;
-    for (int f = 0; f < frames; ++f) ins.push_back(&theta[f]);
-    for (size_t k = 0; k < np; ++k) ins.push_back(&in[k]);
-    if ((rc = contour_overlaps(h, ins, out, (int)np))) return rc;
-
-    // one launch when every plane is on the device and frame f's planes lie f strides behind frame 0's (an [F][K][H][W] block, the
-    // state blocks of a batch); otherwise frame by frame, the single-frame launch
-    bool dev = true;
-    for (int f = 0; f < frames; ++f) dev = dev && mem_of(&theta[f]) == CVS_MEM_DEVICE;
-    for (size_t k = 0; k < np; ++k) dev = dev && mem_of(&in[k]) == CVS_MEM_DEVICE && mem_of(&out[k]) == CVS_MEM_DEVICE;
-    const ptrdiff_t f32 = (ptrdiff_t)sizeof(float);
-    PlaneRun t_run{false, 0}, i_run[kNmsMax], o_run[kNmsMax];
-    bool regular = dev && frames <= 65535;
-    if (regular) {
-        t_run = plane_run(frames, 1, [&](int i, int) { return plane_at(theta[i]); }, true, f32);
-        regular = t_run.ok;
-        for (int k = 0; k < n_maps && regular; ++k) {
-            i_run[k] = plane_run(frames, 1, [&](int i, int) { return plane_at(in[(size_t)i * n_maps + k]); }, true, f32);
-            o_run[k] = plane_run(frames, 1, [&](int i, int) { return plane_at(out[(size_t)i * n_maps + k]); }, false, f32);
-            regular = i_run[k].ok && o_run[k].ok;
-        }
-    }
-    if (!regular) {
-        for (int f = 0; f < frames; ++f)
-            if ((rc = cvs_nonmax(h, &theta[f], n_maps, in + (size_t)f * n_maps, out + (size_t)f * n_maps))) return rc;
-        return CVS_OK;
-    }
-    HIP_TRY(h, hipSetDevice(h->device));
-    h->used = true;
-    NmsArgs a{};
-    NmsBatch b{};
-    a.rows = rows;
-    a.cols = cols;
-    a.n = n_maps;
-    a.theta = {static_cast<float*>(theta[0].data), theta[0].step / sizeof(float)};
-    b.frames = frames;
-    b.theta_stride = t_run.stride / f32;
-    for (int k = 0; k < n_maps; ++k) {
-        a.in[k] = {static_cast<float*>(in[k].data), in[k].step / sizeof(float)};
-        a.out[k] = {static_cast<float*>(out[k].data), out[k].step / sizeof(float)};
-        b.in_stride[k] = i_run[k].stride / f32;
-        b.out_stride[k] = o_run[k].stride / f32;
-    }
-    a.nt_stores = use_nt_stores(h, (size_t)rows * cols * frames);
-    HIP_TRY(h, launch_nonmax_batch(a, b, h->stream));
-    return CVS_OK;
-}
-
-int cvs_hysteresis(cvs_handle h, int n, const cvs_plane* in, float low, float high, const cvs_plane* out, int* passes)
-{
-    if (!h) return CVS_E_BADARG;
-    if (n < 1 || !in || !out) return fail(h, CVS_E_BADARG, "n >= 1 planes, in and out are required");
-    if (std::isnan(low) || std::isnan(high) || low > high) return fail(h, CVS_E_BADARG, "thresholds: low <= high, neither NaN");
-    if (h->rows <= 0) return fail(h, CVS_E_STATE, "no setup yet: the handle has no image size");
-    int rc;
-    const bool u8 = is_u8(&out[0]);
-    for (int k = 0; k < n; ++k) {
-        if ((rc = check_plane(h, &in[k], "in")) || (rc = check_same(h, &in[k], h->rows, h->cols))) return rc;
-        if ((rc = check_plane(h, &out[k], "out", true)) || (rc = check_same(h, &out[k], h->rows, h->cols))) return rc;
-        if (is_u8(&out[k]) != u8) return fail(h, CVS_E_BADARG, "the outputs are all bytes or all f32");
-    }
-    std::vector<const cvs_plane*> ins;
-    for (int k = 0; k < n; ++k) ins.push_back(&in[k]);
-    if ((rc = contour_overlaps(h, ins, out, n))) return rc;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    HIP_TRY(h, hipStreamIsCapturing(h->stream, &cap));
-    if (cap != hipStreamCaptureStatusNone) return fail(h, CVS_E_UNSUPPORTED, "hysteresis reads its pass flag back: not capturable");
-
-    // scratch: the flag word, then kHystMax label planes
-    const int rows = h->rows, cols = h->cols;
-    const size_t lab_pitch = round_up((size_t)cols, 64), lab_stride = round_up(lab_pitch * rows, 256);
-    const size_t need = 256 + (size_t)kHystMax * lab_stride;
-    if (need > h->hy_scr_bytes) HIP_TRY(h, hipSetDevice(h->device));   // (only a call that allocates sets the device: grow_scratch's own condition)
-    if ((rc = grow_scratch(h, "hipMalloc(&h->hy_scr, need)", h->hy_scr, h->hy_scr_bytes, need, 1))) return rc;
-    unsigned* flag = reinterpret_cast<unsigned*>(h->hy_scr);
-    // a pass that is not the last promotes at least one pixel: more passes than pixels (+ the last group) would be a fault of ours
-    const long long max_passes = (long long)rows * cols * kHystMax + 64;
-    int total = 0;
-    for (int z0 = 0; z0 < n; z0 += kHystMax) {
-        const int m = std::min(kHystMax, n - z0);
-        const cvs_plane* pin[kHystMax] = {nullptr, nullptr, nullptr};
-        const cvs_plane* pout[kHystMax] = {nullptr, nullptr, nullptr};   // f32 outputs go through the staging arena
-        for (int k = 0; k < m; ++k) {
-            pin[k] = &in[z0 + k];
-            if (!u8) pout[k] = &out[z0 + k];
-        }
-        Call c;
-        if ((rc = begin(h, c, {pin[0], pin[1], pin[2], pout[0], pout[1], pout[2]}))) return rc;
-        HystArgs a{};
-        a.rows = rows;
-        a.cols = cols;
-        a.n = m;
-        a.low = low;
-        a.high = high;
-        a.lab = h->hy_scr + 256;
-        a.lab_pitch = lab_pitch;
-        a.lab_stride = lab_stride;
-        a.out_u8 = u8 ? 1 : 0;
-        for (int k = 0; k < m; ++k) {
-            if ((rc = in_ref(c, pin[k], a.in[k]))) return rc;
-            const cvs_plane* o = &out[z0 + k];
-            if (!u8) {
-                PlaneRef r;
-                if ((rc = out_ref(c, o, r))) return rc;
-                a.out32[k] = r.p;
-                a.out_pitch[k] = r.pitch;
-            } else if (mem_of(o) == CVS_MEM_DEVICE) {
-                a.out8[k] = reinterpret_cast<unsigned char*>(o->data);
-                a.out_pitch[k] = o->step;
-            } else {   // host bytes: written over the label plane, downloaded from there
-                a.out8[k] = a.lab + (size_t)k * lab_stride;
-                a.out_pitch[k] = lab_pitch;
-            }
-        }
-        HIP_TRY(h, launch_hyst_classify(a, h->stream));
-        // passes in groups (1, 2, 4 .. 16) between read-backs of the flag; the group that changes nothing ends the loop
-        for (int group = 1;; group = std::min(2 * group, 16)) {
-            HIP_TRY(h, launch_hyst_flag_reset(flag, h->stream));
-            for (int i = 0; i < group; ++i) HIP_TRY(h, launch_hyst_pass(a, flag, h->stream));
-            total += group;
-            unsigned changed = 0;
-            HIP_TRY(h, hipMemcpyAsync(&changed, flag, sizeof(changed), hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            if (!changed) break;
-            if (total > max_passes) return fail(h, CVS_E_HIP, "hysteresis did not converge");
-        }
-        HIP_TRY(h, launch_hyst_emit(a, h->stream));
-        if (u8)
-            for (int k = 0; k < m; ++k) {
-                const cvs_plane* o = &out[z0 + k];
-                if (mem_of(o) != CVS_MEM_HOST) continue;
-                HIP_TRY(h, copy_rows(o->data, o->step, a.out8[k], lab_pitch, (size_t)cols, rows, hipMemcpyDeviceToHost, h->stream));
-            }
-        if ((rc = finish(c))) return rc;
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-    }
-    if (passes) *passes = total;
-    return CVS_OK;
 }
 
 int cvs_set_u8_gain(cvs_handle h, float gain)

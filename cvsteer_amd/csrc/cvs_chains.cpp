@@ -6,7 +6,7 @@
 #include <algorithm>
 
 #include "cvs_chains.h"
-#include "cvs_context.h"
+#include "cvs_contour_host.h"
 
 using namespace cvs;
 
@@ -15,32 +15,6 @@ static_assert(CVS_CHAIN_CLOSED == kChainClosed && CVS_CHAIN_HEAD_JUNCTION == kCh
               "the kernels' flag values are the public ones");
 
 namespace {
-
-// a mask plane as the kernels read it: device bytes directly, everything else through in_ref (host planes staged, host bytes widened)
-bool direct_u8(const cvs_plane* p) { return is_u8(p) && mem_of(p) == CVS_MEM_DEVICE; }
-
-int mask_ref(Call& c, const cvs_plane* p, MaskRef& m)
-{
-    if (direct_u8(p)) {
-        m = {p->data, p->step, 1};
-        return CVS_OK;
-    }
-    PlaneRef r;
-    const int rc = in_ref(c, p, r);
-    m = {r.p, r.pitch, 0};
-    return rc;
-}
-
-// sizes first (reserve), then one allocation
-struct Scratch {
-    size_t need = 0;
-    size_t reserve(size_t bytes)
-    {
-        const size_t off = need;
-        need += round_up(bytes, 256);
-        return off;
-    }
-};
 
 int ceil_log2(int n)
 {
@@ -55,19 +29,17 @@ int cvs_contour_chains(cvs_handle h, const cvs_plane* mask, int32_t* points, int
                        int* n_points, int* n_chains)
 {
     if (!h) return CVS_E_BADARG;
-    if (h->rows <= 0) return fail(h, CVS_E_STATE, "no setup yet: the handle has no image size");
-    if ((long long)h->rows * h->cols > (1LL << 28)) return fail(h, CVS_E_SIZE, "more than 2^28 pixels");
     int rc;
-    if ((rc = check_plane(h, mask, "mask", true)) || (rc = check_same(h, mask, h->rows, h->cols))) return rc;
+    if ((rc = need_image(h))) return rc;
+    if ((long long)h->rows * h->cols > (1LL << 28)) return fail(h, CVS_E_SIZE, "more than 2^28 pixels");
+    if ((rc = check_sized(h, mask, "mask", h->rows, h->cols, true))) return rc;
     if (!n_points || !n_chains) return fail(h, CVS_E_BADARG, "n_points and n_chains are required");
     if (point_capacity < 0 || (point_capacity > 0 && !points)) return fail(h, CVS_E_BADARG, "point_capacity >= 0, and points for a capacity > 0");
     if (chain_capacity < 0 || (chain_capacity > 0 && !chains)) return fail(h, CVS_E_BADARG, "chain_capacity >= 0, and chains for a capacity > 0");
     if (mem != CVS_MEM_HOST && mem != CVS_MEM_DEVICE) return fail(h, CVS_E_BADARG, "mem");
     if (reinterpret_cast<uintptr_t>(points) % alignof(int32_t) || reinterpret_cast<uintptr_t>(chains) % alignof(int32_t))
         return fail(h, CVS_E_BADARG, "points / chains not aligned to 4 bytes");
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    HIP_TRY(h, hipStreamIsCapturing(h->stream, &cap));
-    if (cap != hipStreamCaptureStatusNone) return fail(h, CVS_E_UNSUPPORTED, "cvs_contour_chains reads its counts back: not capturable");
+    if ((rc = refuse_capture(h, "cvs_contour_chains reads its counts back: not capturable"))) return rc;
 
     const int rows = h->rows, cols = h->cols, blocks = scan_blocks(rows, cols);
     const size_t npix = (size_t)rows * cols;
@@ -79,7 +51,7 @@ int cvs_contour_chains(cvs_handle h, const cvs_plane* mask, int32_t* points, int
     const size_t o_cnt = sc.reserve(kChCounters * 4), o_part = sc.reserve(((size_t)blocks + 1) * 4);
     Call c;
     if ((rc = begin(h, c, {direct_u8(mask) ? nullptr : mask}))) return rc;
-    if ((rc = grow_scratch(h, "hipMalloc(&h->cc_scr, need)", h->cc_scr, h->cc_scr_bytes, sc.need, 1))) return rc;
+    if ((rc = grow_cc(h, sc.need))) return rc;
     int32_t* parent = reinterpret_cast<int32_t*>(h->cc_scr + o_parent);
     int32_t* aux = reinterpret_cast<int32_t*>(h->cc_scr + o_aux);   // first the node flags at the roots, then the arc bases
     uint16_t* link = reinterpret_cast<uint16_t*>(h->cc_scr + o_link);

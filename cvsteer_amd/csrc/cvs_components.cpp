@@ -7,8 +7,7 @@
 #include <cmath>
 #include <vector>
 
-#include "cvs_components.h"
-#include "cvs_context.h"
+#include "cvs_contour_host.h"
 
 using namespace cvs;
 
@@ -40,52 +39,14 @@ cvs_plane as_words(const cvs_plane* p)
 // before any plane is looked at: the handle has an image size, and its pixels can be indexed with an int32
 int need_size(cvs_handle h)
 {
-    if (h->rows <= 0) return fail(h, CVS_E_STATE, "no setup yet: the handle has no image size");
+    const int rc = need_image(h);
+    if (rc) return rc;
     if ((long long)h->rows * h->cols > 0x7fffffffLL - 1) return fail(h, CVS_E_SIZE, "more than 2^31 - 2 pixels");
     return CVS_OK;
 }
 
-// after every argument check, before the first launch
-int common_checks(cvs_handle h, const char* what)
-{
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    HIP_TRY(h, hipStreamIsCapturing(h->stream, &cap));
-    if (cap != hipStreamCaptureStatusNone) return fail(h, CVS_E_UNSUPPORTED, what);
-    return CVS_OK;
-}
-
-// the handle's component scratch as a bump allocator: sizes first (reserve), then pointers (take)
-struct Scratch {
-    size_t need = 0, used = 0;
-    size_t reserve(size_t bytes)
-    {
-        const size_t off = need;
-        need += round_up(bytes, 256);
-        return off;
-    }
-};
-
-int grow_cc(cvs_handle h, size_t need)
-{
-    if (need > h->cc_scr_bytes) HIP_TRY(h, hipSetDevice(h->device));
-    return grow_scratch(h, "hipMalloc(&h->cc_scr, need)", h->cc_scr, h->cc_scr_bytes, need, 1);
-}
-
-// a mask plane as the tile kernel reads it: device bytes directly, everything else through in_ref (host planes staged, host bytes widened)
-int mask_ref(Call& c, const cvs_plane* p, MaskRef& m)
-{
-    if (is_u8(p) && mem_of(p) == CVS_MEM_DEVICE) {
-        m = {p->data, p->step, 1};
-        return CVS_OK;
-    }
-    PlaneRef r;
-    const int rc = in_ref(c, p, r);
-    m = {r.p, r.pitch, 0};
-    return rc;
-}
-
 // what begin() must reserve in the staging arena for a mask
-const cvs_plane* staged(const cvs_plane* p) { return (is_u8(p) && mem_of(p) == CVS_MEM_DEVICE) ? nullptr : p; }
+const cvs_plane* staged(const cvs_plane* p) { return direct_u8(p) ? nullptr : p; }
 
 // steps 1 and 2 on the handle's stream
 int build_parents(cvs_handle h, const MaskRef& m, int32_t* parent, int32_t* zero_a, uint32_t* zero_b)
@@ -102,12 +63,12 @@ int cvs_label(cvs_handle h, const cvs_plane* mask, const cvs_plane* labels, int*
     if (!h) return CVS_E_BADARG;
     int rc;
     if ((rc = need_size(h))) return rc;
-    if ((rc = check_plane(h, mask, "mask", true)) || (rc = check_same(h, mask, h->rows, h->cols))) return rc;
+    if ((rc = check_sized(h, mask, "mask", h->rows, h->cols, true))) return rc;
     if (!labels) return fail(h, CVS_E_BADARG, "labels");
     if (!is_s32(labels)) return fail(h, CVS_E_BADARG, "labels must be a CVS_DEPTH_S32 plane");
     if ((rc = check_s32(h, labels, "labels")) || (rc = check_same(h, labels, h->rows, h->cols))) return rc;
     if (planes_overlap(mask, labels)) return fail(h, CVS_E_BADARG, "labels overlaps the mask");
-    if ((rc = common_checks(h, "cvs_label reads the count back: not capturable"))) return rc;
+    if ((rc = refuse_capture(h, "cvs_label reads the count back: not capturable"))) return rc;
 
     const int rows = h->rows, cols = h->cols, blocks = scan_blocks(rows, cols);
     const size_t npix = (size_t)rows * cols;
@@ -149,11 +110,11 @@ int cvs_component_stats(cvs_handle h, const cvs_plane* labels, int count, const 
     if (!labels) return fail(h, CVS_E_BADARG, "labels");
     if (!is_s32(labels)) return fail(h, CVS_E_BADARG, "labels must be a CVS_DEPTH_S32 plane");
     if ((rc = check_s32(h, labels, "labels")) || (rc = check_same(h, labels, h->rows, h->cols))) return rc;
-    if (weight && ((rc = check_plane(h, weight, "weight")) || (rc = check_same(h, weight, h->rows, h->cols)))) return rc;
+    if (weight && (rc = check_sized(h, weight, "weight", h->rows, h->cols))) return rc;
     if (count < 0 || (count > 0 && !table)) return fail(h, CVS_E_BADARG, "count >= 0, and a table for count > 0");
     if (table_mem != CVS_MEM_HOST && table_mem != CVS_MEM_DEVICE) return fail(h, CVS_E_BADARG, "table_mem");
     if (reinterpret_cast<uintptr_t>(table) % alignof(int32_t)) return fail(h, CVS_E_BADARG, "table not aligned to 4 bytes");
-    if ((rc = common_checks(h, "cvs_component_stats returns with the table written: not capturable"))) return rc;
+    if ((rc = refuse_capture(h, "cvs_component_stats returns with the table written: not capturable"))) return rc;
     if (count == 0) return CVS_OK;
 
     const int rows = h->rows, cols = h->cols;
@@ -191,19 +152,15 @@ int cvs_contour_prune(cvs_handle h, int n, const cvs_plane* mask, const cvs_plan
     if ((rc = need_size(h))) return rc;
     const bool u8 = is_u8(&out[0]);
     for (int k = 0; k < n; ++k) {
-        if ((rc = check_plane(h, &mask[k], "mask", true)) || (rc = check_same(h, &mask[k], h->rows, h->cols))) return rc;
-        if (weight && ((rc = check_plane(h, &weight[k], "weight")) || (rc = check_same(h, &weight[k], h->rows, h->cols)))) return rc;
-        if ((rc = check_plane(h, &out[k], "out", true)) || (rc = check_same(h, &out[k], h->rows, h->cols))) return rc;
+        if ((rc = check_sized(h, &mask[k], "mask", h->rows, h->cols, true))) return rc;
+        if (weight && (rc = check_sized(h, &weight[k], "weight", h->rows, h->cols))) return rc;
+        if ((rc = check_sized(h, &out[k], "out", h->rows, h->cols, true))) return rc;
         if (is_u8(&out[k]) != u8) return fail(h, CVS_E_BADARG, "the outputs are all bytes or all f32");
     }
-    for (int k = 0; k < n; ++k) {
-        for (int j = 0; j < n; ++j) {
-            if (planes_overlap(&out[k], &mask[j]) || (weight && planes_overlap(&out[k], &weight[j])))
-                return fail(h, CVS_E_BADARG, "an output plane overlaps an input plane");
-            if (j > k && planes_overlap(&out[k], &out[j])) return fail(h, CVS_E_BADARG, "two output planes overlap each other");
-        }
-    }
-    if ((rc = common_checks(h, "cvs_contour_prune reads its counts back: not capturable"))) return rc;
+    std::vector<cvs_plane> ins(mask, mask + n);
+    if (weight) ins.insert(ins.end(), weight, weight + n);
+    if ((rc = check_disjoint(h, ins.data(), ins.size(), out, (size_t)n))) return rc;
+    if ((rc = refuse_capture(h, "cvs_contour_prune reads its counts back: not capturable"))) return rc;
 
     const int rows = h->rows, cols = h->cols;
     const size_t npix = (size_t)rows * cols, bpitch = round_up((size_t)cols, 64);
@@ -240,26 +197,13 @@ int cvs_contour_prune(cvs_handle h, int n, const cvs_plane* mask, const cvs_plan
         e.min_peak = min_peak;
         e.out_u8 = u8 ? 1 : 0;
         e.kept = dkept + k;
-        const bool host_bytes = u8 && mem_of(o) == CVS_MEM_HOST;
-        if (!u8) {
-            PlaneRef r;
-            if ((rc = out_ref(c, o, r))) return rc;
-            e.out = r.p;
-            e.out_pitch = r.pitch;
-        } else if (host_bytes) {
-            e.out = dbytes;
-            e.out_pitch = bpitch;
-        } else {
-            e.out = o->data;
-            e.out_pitch = o->step;
-        }
+        if ((rc = mask_out(c, o, u8, dbytes, bpitch, e.out, e.out_pitch))) return rc;
         if ((rc = build_parents(h, m, parent, area, peak))) return rc;
         HIP_TRY(h, launch_cc_flatten(rows, cols, parent, root, h->stream));
         HIP_TRY(h, launch_prune_stats(rows, cols, root, wr, area, peak, h->stream));
         HIP_TRY(h, launch_prune_emit(e, h->stream));
-        if (host_bytes) HIP_TRY(h, copy_rows(o->data, o->step, dbytes, bpitch, (size_t)cols, rows, hipMemcpyDeviceToHost, h->stream));
-        if ((rc = finish(c))) return rc;
-        if (host_bytes) HIP_TRY(h, hipStreamSynchronize(h->stream));   // the staging bytes are reused by the next plane
+        if ((rc = fetch_mask(c, o, u8, e.out, e.out_pitch)) || (rc = finish(c))) return rc;
+        if (staged_bytes(o, u8)) HIP_TRY(h, hipStreamSynchronize(h->stream));   // the staging bytes are reused by the next plane
     }
     std::vector<int> counts((size_t)n);
     HIP_TRY(h, hipMemcpyAsync(counts.data(), dkept, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
@@ -280,7 +224,7 @@ int cvs_contour_points(cvs_handle h, const cvs_plane* labels, int32_t* points, i
     if (capacity < 0 || (capacity > 0 && !points)) return fail(h, CVS_E_BADARG, "capacity >= 0, and points for capacity > 0");
     if (points_mem != CVS_MEM_HOST && points_mem != CVS_MEM_DEVICE) return fail(h, CVS_E_BADARG, "points_mem");
     if (reinterpret_cast<uintptr_t>(points) % alignof(int32_t)) return fail(h, CVS_E_BADARG, "points not aligned to 4 bytes");
-    if ((rc = common_checks(h, "cvs_contour_points reads the number of points back: not capturable"))) return rc;
+    if ((rc = refuse_capture(h, "cvs_contour_points reads the number of points back: not capturable"))) return rc;
 
     const int rows = h->rows, cols = h->cols, blocks = scan_blocks(rows, cols);
     const bool host_points = points_mem == CVS_MEM_HOST;

@@ -1,7 +1,8 @@
 // cvs_context.h -- the handle behind the C ABI and the host-side helpers its translation units share.
 // Internal: cvs_api.cpp (entry points, do_setup), cvs_pipeline.cpp (caller pipeline, 8-bit routes), cvs_handle.cpp (argument checks,
 // staging arena, state blocks), cvs_tune.cpp (launch configuration), cvs_host.cpp (overlapped host path); cvs_layout.h (how planes lie
-// in memory) stands apart: no handle, no device.  The public boundary is include/cvsteer_hip.h.
+// in memory) stands apart: no handle, no device.  The contour tail (cvs_contour.cpp: thinning; cvs_components.cpp, cvs_link.cpp,
+// cvs_chains.cpp, cvs_polyline.cpp) adds the helpers of cvs_contour_host.h on top.  The public boundary is include/cvsteer_hip.h.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -147,6 +148,10 @@ int check_plane(cvs_handle h, const cvs_plane* p, const char* name, bool allow_u
 bool planes_overlap(const cvs_plane* a, const cvs_plane* b);
 int check_no_overlap(cvs_handle h, const cvs_plane* input, const cvs_plane* const* outs, int n);
 int check_point_overlaps(cvs_handle h, std::initializer_list<const cvs_plane*> ins, std::initializer_list<const cvs_plane*> outs);
+// the contour tail's rule: an output shares no byte with any input (it may not BE one either) nor with another output; inputs may share
+// memory with each other, planes without data are skipped.  find_overlap: the message of the first overlap found, or nullptr
+const char* find_overlap(const cvs_plane* ins, size_t n_in, const cvs_plane* outs, size_t n_out);
+int check_disjoint(cvs_handle h, const cvs_plane* ins, size_t n_in, const cvs_plane* outs, size_t n_out);
 int check_same(cvs_handle h, const cvs_plane* p, int rows, int cols);
 int arena_reserve(cvs_handle h, size_t elems);
 float* arena_take(cvs_handle h, size_t elems);
@@ -230,5 +235,6 @@ struct SetupReq {
     const U8Req* u8 = nullptr;                       // with pipe_outs: 8-bit three-maps launch, or kNotFused
 };
 int do_setup(cvs_handle h, const SetupReq& rq);
+int need_state(cvs_handle h, bool orient);   // CVS_E_STATE without a setup (orient: without CVS_SETUP_ORIENT)
 
 }  // namespace cvs

@@ -1,0 +1,53 @@
+// cvs_contour_host.h -- what the host units of the contour tail share in front of their kernels (cvs_contour.cpp, which defines it,
+// cvs_components.cpp, cvs_link.cpp, cvs_chains.cpp, cvs_polyline.cpp): the checks every entry point begins with, the handle's scratch as a
+// bump allocator, and the routes of mask inputs and mask outputs.  Internal; the overlap rule of the tail is check_disjoint (cvs_context.h).
+#pragma once
+#include <algorithm>
+
+#include "cvs_components.h"
+#include "cvs_context.h"
+
+namespace cvs {
+
+// ---- checks ----
+int need_image(cvs_handle h);   // CVS_E_STATE before the first setup: the handle has no image size (each caller's pixel limit is its own)
+int check_sized(cvs_handle h, const cvs_plane* p, const char* name, int rows, int cols, bool allow_u8 = false);   // check_plane, then check_same
+int capturing(cvs_handle h, bool& yes);               // is the handle's stream being captured?
+int refuse_capture(cvs_handle h, const char* what);   // CVS_E_UNSUPPORTED with `what` when it is: after every argument check, before the first launch
+
+// a device f32 plane of the engine's own (a state plane, a plane of the handle's scratch) as a cvs_plane
+inline cvs_plane device_plane(float* p, int rows, int cols, size_t pitch_elems)
+{
+    cvs_plane q{};
+    q.data = p;
+    q.rows = rows;
+    q.cols = cols;
+    q.step = pitch_elems * sizeof(float);
+    q.mem = CVS_MEM_DEVICE;
+    return q;
+}
+
+// ---- the handle's scratch as a bump allocator: sizes first (reserve), then one allocation ----
+struct Scratch {
+    size_t need = 0;
+    size_t reserve(size_t bytes)
+    {
+        const size_t off = need;
+        need += round_up(std::max<size_t>(bytes, 1), 256);
+        return off;
+    }
+};
+int grow_cc(cvs_handle h, size_t need);   // cvs_context::cc_scr of at least `need` bytes (only a call that allocates sets the device)
+
+// ---- mask inputs: device bytes are read directly, everything else through in_ref (host planes staged, host bytes widened) ----
+inline bool direct_u8(const cvs_plane* p) { return is_u8(p) && mem_of(p) == CVS_MEM_DEVICE; }   // (nothing for begin() to reserve)
+int mask_ref(Call& c, const cvs_plane* p, MaskRef& m);
+
+// ---- mask outputs: f32 planes through out_ref, device bytes directly, host bytes into `slot` (rows of slot_pitch bytes in the handle's
+// scratch) and from there to the caller with fetch_mask, behind the launch that wrote them.  p / pitch: what the kernel's descriptor holds,
+// the pitch in elements of the output's own type ----
+inline bool staged_bytes(const cvs_plane* o, bool u8) { return u8 && mem_of(o) == CVS_MEM_HOST; }
+int mask_out(Call& c, const cvs_plane* o, bool u8, unsigned char* slot, size_t slot_pitch, void*& p, size_t& pitch);
+int fetch_mask(Call& c, const cvs_plane* o, bool u8, const void* p, size_t pitch);   // queues the copy; the caller synchronises
+
+}  // namespace cvs

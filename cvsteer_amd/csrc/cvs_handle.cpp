@@ -143,6 +143,41 @@ int check_point_overlaps(cvs_handle h, std::initializer_list<const cvs_plane*> i
     return CVS_OK;
 }
 
+// The contour kernels read the neighbours of the pixel they write: does an output share a byte with an input or with another output?  The
+// planes are sorted by address and each is compared with the planes that begin before it ends: n log n for planes that lie apart (the
+// usual case, whatever n), exact (planes_overlap) for those whose address ranges interleave.
+const char* find_overlap(const cvs_plane* ins, size_t n_in, const cvs_plane* outs, size_t n_out)
+{
+    struct Span {
+        uintptr_t lo, hi;
+        const cvs_plane* p;
+        bool out;
+    };
+    std::vector<Span> v;
+    v.reserve(n_in + n_out);
+    auto add = [&](const cvs_plane* p, bool out) {
+        if (!p->data) return;
+        const uintptr_t lo = reinterpret_cast<uintptr_t>(p->data);
+        v.push_back({lo, lo + (size_t)(p->rows - 1) * p->step + (size_t)p->cols * (is_u8(p) ? 1 : sizeof(float)), p, out});
+    };
+    for (size_t k = 0; k < n_in; ++k) add(&ins[k], false);
+    for (size_t k = 0; k < n_out; ++k) add(&outs[k], true);
+    std::sort(v.begin(), v.end(), [](const Span& a, const Span& b) { return a.lo < b.lo; });
+    for (size_t i = 0; i < v.size(); ++i)
+        for (size_t j = i + 1; j < v.size() && v[j].lo < v[i].hi; ++j) {
+            if (!v[i].out && !v[j].out) continue;   // inputs may share memory with each other
+            if (planes_overlap(v[i].p, v[j].p))
+                return (v[i].out && v[j].out) ? "two output planes overlap each other" : "an output plane overlaps an input plane";
+        }
+    return nullptr;
+}
+
+int check_disjoint(cvs_handle h, const cvs_plane* ins, size_t n_in, const cvs_plane* outs, size_t n_out)
+{
+    const char* msg = find_overlap(ins, n_in, outs, n_out);
+    return msg ? fail(h, CVS_E_BADARG, msg) : CVS_OK;
+}
+
 int check_same(cvs_handle h, const cvs_plane* p, int rows, int cols)
 {
     if (p->rows != rows || p->cols != cols) return fail(h, CVS_E_SIZE, "plane size mismatch");

@@ -7,7 +7,7 @@
 #include <cmath>
 #include <vector>
 
-#include "cvs_context.h"
+#include "cvs_contour_host.h"
 #include "cvs_layout.h"
 #include "cvs_link.h"
 
@@ -26,36 +26,6 @@ int chain_planes(size_t plane_stride, bool any_host)
     return (int)m;
 }
 
-
-// Does an output share a byte with an input or with another output?  The planes are sorted by address and each is compared with the planes
-// that begin before it ends: n log n for planes that lie apart (the usual case, whatever n), exact (planes_overlap) for those whose address
-// ranges interleave.  Returns the message of the first overlap found, or nullptr.
-const char* find_overlap(const cvs_plane* ins, size_t n_in, const cvs_plane* outs, size_t n_out)
-{
-    struct Span {
-        uintptr_t lo, hi;
-        const cvs_plane* p;
-        bool out;
-    };
-    std::vector<Span> v;
-    v.reserve(n_in + n_out);
-    auto add = [&](const cvs_plane* p, bool out) {
-        if (!p->data) return;
-        const uintptr_t lo = reinterpret_cast<uintptr_t>(p->data);
-        v.push_back({lo, lo + (size_t)(p->rows - 1) * p->step + (size_t)p->cols * (is_u8(p) ? 1 : sizeof(float)), p, out});
-    };
-    for (size_t k = 0; k < n_in; ++k) add(&ins[k], false);
-    for (size_t k = 0; k < n_out; ++k) add(&outs[k], true);
-    std::sort(v.begin(), v.end(), [](const Span& a, const Span& b) { return a.lo < b.lo; });
-    for (size_t i = 0; i < v.size(); ++i)
-        for (size_t j = i + 1; j < v.size() && v[j].lo < v[i].hi; ++j) {
-            if (!v[i].out && !v[j].out) continue;   // inputs may share memory with each other
-            if (planes_overlap(v[i].p, v[j].p))
-                return (v[i].out && v[j].out) ? "two output planes overlap each other" : "an output plane overlaps an input plane";
-        }
-    return nullptr;
-}
-
 }  // namespace
 
 extern "C" {
@@ -67,39 +37,37 @@ int cvs_link(cvs_handle h, int n, const cvs_plane* in, float low, float high, in
     if (n < 1 || !in || !out) return fail(h, CVS_E_BADARG, "n >= 1 planes, in and out are required");
     if (std::isnan(low) || std::isnan(high) || low > high) return fail(h, CVS_E_BADARG, "thresholds: low <= high, neither NaN");
     if (min_area < 0 || std::isnan(min_peak)) return fail(h, CVS_E_BADARG, "min_area >= 0, min_peak not NaN");
-    if (h->rows <= 0) return fail(h, CVS_E_STATE, "no setup yet: the handle has no image size");
+    int rc;
+    if ((rc = need_image(h))) return rc;
     const int rows = h->rows, cols = h->cols;
     if ((long long)rows * cols > 0x7fffffffLL - 1 || (rows + kCcTileH - 1) / kCcTileH > 65535)
         return fail(h, CVS_E_SIZE, "more than 2^31 - 2 pixels, or more rows than one launch can tile");
-    int rc;
     const bool u8 = is_u8(&out[0]);
     bool any_host = false;
     for (int k = 0; k < n; ++k) {
-        if ((rc = check_plane(h, &in[k], "in")) || (rc = check_same(h, &in[k], rows, cols))) return rc;
-        if ((rc = check_plane(h, &out[k], "out", true)) || (rc = check_same(h, &out[k], rows, cols))) return rc;
+        if ((rc = check_sized(h, &in[k], "in", rows, cols)) || (rc = check_sized(h, &out[k], "out", rows, cols, true))) return rc;
         if (is_u8(&out[k]) != u8) return fail(h, CVS_E_BADARG, "the outputs are all bytes or all f32");
         any_host = any_host || mem_of(&in[k]) == CVS_MEM_HOST || mem_of(&out[k]) == CVS_MEM_HOST;
     }
-    if (const char* msg = find_overlap(in, (size_t)n, out, (size_t)n)) return fail(h, CVS_E_BADARG, msg);
+    if ((rc = check_disjoint(h, in, (size_t)n, out, (size_t)n))) return rc;
     if (kept_dev && reinterpret_cast<uintptr_t>(kept_dev) % alignof(int32_t)) return fail(h, CVS_E_BADARG, "kept_dev not aligned to 4 bytes");
 
     // scratch of one chain: parent, area and peak of its planes, the descriptor table, byte staging of host outputs
     const size_t npix = (size_t)rows * cols, plane_stride = round_up(npix, 64), bpitch = round_up((size_t)cols, 64);
     const int per_chain = std::min(n, chain_planes(plane_stride, any_host));
-    const size_t o_parent = 0, o_area = o_parent + (size_t)per_chain * plane_stride * 4, o_peak = o_area + (size_t)per_chain * plane_stride * 4;
-    const size_t o_tab = o_peak + (size_t)per_chain * plane_stride * 4;
-    const size_t o_bytes = o_tab + round_up((size_t)per_chain * sizeof(LinkDesc), 256);
-    const size_t bstride = round_up(bpitch * rows, 256);
-    const size_t need = o_bytes + ((u8 && any_host) ? (size_t)per_chain * bstride : 0);
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    HIP_TRY(h, hipStreamIsCapturing(h->stream, &cap));
-    if (cap != hipStreamCaptureStatusNone) {
+    const size_t words = (size_t)per_chain * plane_stride * 4, bstride = round_up(bpitch * rows, 256);
+    Scratch sc;
+    const size_t o_parent = sc.reserve(words), o_area = sc.reserve(words), o_peak = sc.reserve(words);
+    const size_t o_tab = sc.reserve((size_t)per_chain * sizeof(LinkDesc));
+    const size_t o_bytes = (u8 && any_host) ? sc.reserve((size_t)per_chain * bstride) : 0;
+    bool cap = false;
+    if ((rc = capturing(h, cap))) return rc;
+    if (cap) {
         if (any_host) return fail(h, CVS_E_UNSUPPORTED, "cvs_link with host planes copies and synchronises: not capturable");
-        if (need > h->cc_scr_bytes)
+        if (sc.need > h->cc_scr_bytes)
             return fail(h, CVS_E_UNSUPPORTED, "cvs_link would have to grow the handle's scratch during capture: call once eagerly first");
     }
-    if (need > h->cc_scr_bytes) HIP_TRY(h, hipSetDevice(h->device));
-    if ((rc = grow_scratch(h, "hipMalloc(&h->cc_scr, need)", h->cc_scr, h->cc_scr_bytes, need, 1))) return rc;
+    if ((rc = grow_cc(h, sc.need))) return rc;
     LinkDesc* dtab = reinterpret_cast<LinkDesc*>(h->cc_scr + o_tab);
 
     std::vector<LinkDesc> desc((size_t)per_chain);
@@ -115,17 +83,7 @@ int cvs_link(cvs_handle h, int n, const cvs_plane* in, float low, float high, in
             if ((rc = in_ref(c, &in[z0 + k], r))) return rc;
             desc[k].in = r.p;
             desc[k].in_pitch = r.pitch;
-            if (!u8) {
-                if ((rc = out_ref(c, o, r))) return rc;
-                desc[k].out = r.p;
-                desc[k].out_pitch = r.pitch;
-            } else if (mem_of(o) == CVS_MEM_HOST) {
-                desc[k].out = h->cc_scr + o_bytes + (size_t)k * bstride;
-                desc[k].out_pitch = bpitch;
-            } else {
-                desc[k].out = o->data;
-                desc[k].out_pitch = o->step;
-            }
+            if ((rc = mask_out(c, o, u8, h->cc_scr + o_bytes + (size_t)k * bstride, bpitch, desc[k].out, desc[k].out_pitch))) return rc;
         }
         LinkArgs a{};
         a.rows = rows;
@@ -164,13 +122,10 @@ int cvs_link(cvs_handle h, int n, const cvs_plane* in, float low, float high, in
         HIP_TRY(h, launch_link_borders(a, h->stream));
         HIP_TRY(h, launch_link_stats(a, h->stream));
         HIP_TRY(h, launch_link_emit(a, h->stream));
-        if (u8)
-            for (int k = 0; k < m; ++k) {
-                const cvs_plane* o = &out[z0 + k];
-                if (mem_of(o) != CVS_MEM_HOST) continue;
-                HIP_TRY(h, copy_rows(o->data, o->step, desc[k].out, bpitch, (size_t)cols, rows, hipMemcpyDeviceToHost, h->stream));
-                c.touched_host = true;
-            }
+        for (int k = 0; k < m; ++k) {
+            if ((rc = fetch_mask(c, &out[z0 + k], u8, desc[k].out, desc[k].out_pitch))) return rc;
+            if (staged_bytes(&out[z0 + k], u8)) c.touched_host = true;
+        }
         if ((rc = finish(c))) return rc;   // host planes: the data has landed, and the staging of the next chain may reuse the memory
     }
     return CVS_OK;
@@ -191,11 +146,11 @@ int cvs_contours_batch(cvs_handle h, const cvs_plane* images, int n, float low, 
     std::vector<cvs_plane> want_out;
     std::vector<size_t> want_idx;
     for (int i = 0; i < n; ++i) {
-        if ((rc = check_plane(h, &images[i], "image", true)) || (rc = check_same(h, &images[i], rows, cols))) return rc;
+        if ((rc = check_sized(h, &images[i], "image", rows, cols, true))) return rc;
         for (int k = 0; k < 3; ++k) {
             const cvs_plane* o = &outs[(size_t)i * 3 + k];
             if (!o->data) continue;
-            if ((rc = check_plane(h, o, "out", true)) || (rc = check_same(h, o, rows, cols))) return rc;
+            if ((rc = check_sized(h, o, "out", rows, cols, true))) return rc;
             want_out.push_back(*o);
             want_idx.push_back((size_t)i * 3 + k);
         }
@@ -203,20 +158,12 @@ int cvs_contours_batch(cvs_handle h, const cvs_plane* images, int n, float low, 
     for (size_t k = 0; k < want_out.size(); ++k)
         if (is_u8(&want_out[k]) != is_u8(&want_out[0])) return fail(h, CVS_E_BADARG, "the outputs are all bytes or all f32");
     // every output against the image of EVERY frame and against every other output
-    if (const char* msg = find_overlap(images, (size_t)n, want_out.data(), want_out.size())) return fail(h, CVS_E_BADARG, msg);
+    if ((rc = check_disjoint(h, images, (size_t)n, want_out.data(), want_out.size()))) return rc;
     // the handle's own planes: [n][3] maps and [n][3] thinned maps, dense rows of `pitch` elements
     const size_t pitch = round_up((size_t)cols, 64), plane = pitch * rows, total = (size_t)n * 6 * plane;
     if (total > h->ct_scr_elems) HIP_TRY(h, hipSetDevice(h->device));
     if ((rc = grow_scratch(h, "hipMalloc(&h->ct_scr, total * sizeof(float))", h->ct_scr, h->ct_scr_elems, total, sizeof(float)))) return rc;
-    auto own = [&](size_t idx) {
-        cvs_plane p{};
-        p.data = h->ct_scr + idx * plane;
-        p.rows = rows;
-        p.cols = cols;
-        p.step = pitch * sizeof(float);
-        p.mem = CVS_MEM_DEVICE;
-        return p;
-    };
+    auto own = [&](size_t idx) { return device_plane(h->ct_scr + idx * plane, rows, cols, pitch); };
     std::vector<cvs_plane> pipe_outs((size_t)n * 8), maps((size_t)n * 3), thin((size_t)n * 3);
     for (int i = 0; i < n; ++i)
         for (int k = 0; k < 3; ++k) {

@@ -6,7 +6,7 @@
 #include <algorithm>
 #include <cmath>
 
-#include "cvs_context.h"
+#include "cvs_contour_host.h"
 #include "cvs_polyline.h"
 
 using namespace cvs;
@@ -14,17 +14,6 @@ using namespace cvs;
 static_assert(sizeof(cvs_chain) == 16, "cvs_chain: four 4-byte fields (k_pl_apply writes it as four words)");
 
 namespace {
-
-// sizes first (reserve), then one allocation
-struct Scratch {
-    size_t need = 0;
-    size_t reserve(size_t bytes)
-    {
-        const size_t off = need;
-        need += round_up(std::max<size_t>(bytes, 1), 256);
-        return off;
-    }
-};
 
 bool misaligned(const void* p) { return reinterpret_cast<uintptr_t>(p) % alignof(int32_t) != 0; }
 
@@ -49,9 +38,8 @@ int cvs_chain_polylines(cvs_handle h, const int32_t* points, int n_points, const
         for (int c = 0; c < n_chains; ++c)
             if (chains[c].start < 0 || chains[c].length < 1 || (long long)chains[c].start + chains[c].length > n_points)
                 return fail(h, CVS_E_BADARG, "a chain does not lie inside points");
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    HIP_TRY(h, hipStreamIsCapturing(h->stream, &cap));
-    if (cap != hipStreamCaptureStatusNone) return fail(h, CVS_E_UNSUPPORTED, "cvs_chain_polylines reads its count back: not capturable");
+    int rc;
+    if ((rc = refuse_capture(h, "cvs_chain_polylines reads its count back: not capturable"))) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     h->used = true;
     if (n_chains == 0) {
@@ -67,7 +55,6 @@ int cvs_chain_polylines(cvs_handle h, const int32_t* points, int n_points, const
     const size_t o_pts = host ? sc.reserve((size_t)n_points * 8) : 0, o_chn = host ? sc.reserve((size_t)n_chains * sizeof(cvs_chain)) : 0;
     const size_t o_vtx = host ? sc.reserve((size_t)cap_v * 8) : 0, o_idx = host && index ? sc.reserve((size_t)cap_v * 4) : 0;
     const size_t o_pol = host ? sc.reserve((size_t)n_chains * sizeof(cvs_chain)) : 0;
-    int rc;
     if ((rc = grow_scratch(h, "hipMalloc(&h->ch_scr, need)", h->ch_scr, h->ch_scr_bytes, sc.need, 1))) return rc;
     uint8_t* keep = h->ch_scr + o_keep;
     int32_t* cnt = reinterpret_cast<int32_t*>(h->ch_scr + o_cnt);

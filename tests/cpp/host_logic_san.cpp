@@ -1,6 +1,7 @@
 // host_logic_san.cpp -- the host logic of libcvsteer_hip.so that needs no device, under AddressSanitizer +
 // UndefinedBehaviorSanitizer: argument checks (check_plane), the overlap rules of include/cvsteer_hip.h (planes_overlap against
-// a byte-for-byte model on random views), the CVS_OPTS parser on hostile strings, the state layout arithmetic (layout_state on
+// a byte-for-byte model on random views; find_overlap, the contour tail's sorted check, against the plain loop over planes_overlap), the
+// CVS_OPTS parser on hostile strings, the state layout arithmetic (layout_state on
 // every kind / size / grouping: offsets inside the block, no two planes sharing an element), the plane-run and one-resource classifier
 // of cvs_layout.h (a table of layouts with the answer every call site gave before it existed) and the tap generator.  A cvs_context is
 // a plain struct: it is built here without a HIP call; no entry point that touches the device is called.
@@ -86,6 +87,61 @@ int main()
     const cvs_plane* outs[3] = {&ok, nullptr, &ok};
     REQUIRE(check_no_overlap(h, nullptr, outs, 3) == CVS_E_BADARG);   // an output given twice
     REQUIRE(check_point_overlaps(h, {&ok}, {&ok}) == CVS_OK);          // in place: an output may BE an input
+
+    // ---- find_overlap (the contour tail's rule) against the quadratic loop over planes_overlap: random views into the arena and into a second
+    // arena "of the other memory kind" (addresses of the two kinds may interleave, their planes never overlap), some without data ----
+    {
+        static unsigned char other[4096];
+        const char* const kIn = "an output plane overlaps an input plane";
+        const char* const kOut = "two output planes overlap each other";
+        auto same = [](const char* a, const char* b) { return (!a && !b) || (a && b && !std::strcmp(a, b)); };
+        auto view = [&]() {
+            const bool u8 = rnd() & 1, dev = rnd() % 4 == 0;
+            const int es = u8 ? 1 : 4;
+            const int rows = 1 + rnd() % 6, cols = 1 + rnd() % 6;
+            const size_t step = (size_t)(cols + rnd() % 5) * es;
+            const size_t span = (size_t)(rows - 1) * step + (size_t)cols * es;
+            // one time in three near the start of the arena, so that cases with several overlaps are common
+            const size_t off = (rnd() % (rnd() % 3 ? sizeof arena - span : 256)) / es * es;
+            cvs_plane v{reinterpret_cast<float*>((dev ? other : arena) + off), rows, cols, step, (dev ? CVS_MEM_DEVICE : CVS_MEM_HOST) | (u8 ? CVS_DEPTH_U8 : 0)};
+            if (rnd() % 8 == 0) v.data = nullptr;
+            return v;
+        };
+        int refused = 0, both = 0;
+        for (int it = 0; it < 6000; ++it) {
+            cvs_plane ins[4], outs[4];
+            const size_t n_in = rnd() % 5, n_out = 1 + rnd() % 4;
+            for (size_t k = 0; k < n_in; ++k) ins[k] = view();
+            for (size_t k = 0; k < n_out; ++k) outs[k] = view();
+            bool with_in = false, with_out = false;
+            for (size_t k = 0; k < n_out; ++k) {
+                for (size_t j = 0; j < n_in; ++j) with_in = with_in || planes_overlap(&outs[k], &ins[j]);
+                for (size_t j = k + 1; j < n_out; ++j) with_out = with_out || planes_overlap(&outs[k], &outs[j]);
+            }
+            const char* msg = find_overlap(ins, n_in, outs, n_out);
+            REQUIRE((msg != nullptr) == (with_in || with_out));
+            if (with_in != with_out) REQUIRE(same(msg, with_in ? kIn : kOut));
+            if (msg) REQUIRE(same(msg, kIn) || same(msg, kOut));
+            REQUIRE(check_disjoint(h, ins, n_in, outs, n_out) == (msg ? CVS_E_BADARG : CVS_OK));
+            refused += msg != nullptr;
+            both += with_in && with_out;
+        }
+        REQUIRE(refused > 600 && refused < 5400 && both > 60);   // (the generator exercises every verdict)
+        // the cases the three former call sites were written for
+        const cvs_plane twice[2] = {ok, ok};
+        REQUIRE(same(find_overlap(nullptr, 0, twice, 2), kOut));                      // an output given twice
+        REQUIRE(same(find_overlap(&ok, 1, &ok, 1), kIn));                             // an output that IS an input: refused here
+        cvs_plane apart = ok;
+        apart.data = buf + 1024;
+        REQUIRE(find_overlap(twice, 2, &apart, 1) == nullptr);                        // two inputs that are the same plane
+        const cvs_plane left{buf, 8, 8, 16 * sizeof(float), CVS_MEM_HOST}, right{buf + 8, 8, 8, 16 * sizeof(float), CVS_MEM_HOST};
+        REQUIRE(find_overlap(&left, 1, &right, 1) == nullptr);                        // side-by-side ROI views with one step
+        const cvs_plane lr[2] = {left, right};
+        REQUIRE(find_overlap(nullptr, 0, lr, 2) == nullptr);
+        cvs_plane none = ok;
+        none.data = nullptr;
+        REQUIRE(find_overlap(&none, 1, &ok, 1) == nullptr && find_overlap(&ok, 1, &none, 1) == nullptr);   // planes without data are skipped
+    }
 
     // ---- CVS_OPTS: hostile strings ----
     const char* opts[] = {"", ",", "=", "autotune", "autotune=", "=3", "autotune=0,layout=9,pyr_strip=-4,batch_ways=99999999999999999999,read_ahead=x",
@@ -228,6 +284,6 @@ int main()
     REQUIRE(host_make_taps(7, 0, 4, 0.67f, t) != 0 && host_make_taps(CVS_KIND_G2, 7, 4, 0.67f, t) != 0 && host_make_taps(CVS_KIND_G2, 0, kMaxWidth + 1, 0.67f, t) != 0);
     float w[kMaxBasis];
     for (float th : {0.f, 0.3f, -1.2f, 3.1415927f}) REQUIRE(host_steer_weights(CVS_KIND_G2, th, w) == 0 && host_steer_weights(CVS_KIND_G4, th, w) == 0);
-    std::printf("host_logic_san: argument checks, 20000 overlap cases, CVS_OPTS fuzz, 480 state layouts, 14 plane layouts, taps: no sanitizer report\n");
+    std::printf("host_logic_san: argument checks, 20000 + 6000 overlap cases, CVS_OPTS fuzz, 480 state layouts, 14 plane layouts, taps: no sanitizer report\n");
     return 0;
 }

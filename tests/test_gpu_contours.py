@@ -194,6 +194,31 @@ def test_hysteresis_thinned_fish_and_three_at_once(fish):
         assert torch.equal(g, f.hysteresis(t, low, high))
 
 
+@pytest.mark.parametrize("where, dtype", [("host", np.uint8), ("host", np.float32), ("device-padded", torch.uint8), ("device", torch.float32)])
+def test_hysteresis_two_groups_every_output_route(where, dtype):
+    """4 planes of 37 x 70: more than the three planes of one group, so the second group reuses the label scratch; 70 columns are no
+    multiple of 64, so host bytes are staged at a pitch that is not the row width.  Host bytes, host f32, device bytes with padded rows
+    (column slices of a wider tensor, whose padding stays as it was) and device f32."""
+    rows, cols, low, high = 37, 70, 0.5, 0.9
+    rng = np.random.default_rng(3770)
+    vs = [rng.random((rows, cols), dtype=np.float32) for _ in range(4)]
+    f = _g2(torch.from_numpy(rand_image(rows, cols)).to(DEV))
+    if where == "host":
+        got = f.hysteresis(vs, low, high, dtype=dtype)
+        assert all(isinstance(g, np.ndarray) and g.dtype == dtype for g in got)
+    else:
+        dvs = [torch.from_numpy(v).to(DEV) for v in vs]
+        wide = torch.full((4, rows, cols + 26), 7, dtype=dtype, device=DEV) if where == "device-padded" else None
+        out = None if wide is None else [wide[k, :, :cols] for k in range(4)]
+        got = f.hysteresis(dvs, low, high, dtype=dtype, out=out)
+        assert all(g.is_cuda and g.dtype == dtype for g in got)
+        if wide is not None:
+            assert all(g.stride(0) == cols + 26 for g in got) and bool((wide[:, :, cols:] == 7).all())
+    assert len(got) == 4
+    for g, v in zip(got, vs):
+        _check_hyst(g, v, low, high)
+
+
 def test_hysteresis_serpentine():
     """a 1-pixel path across a 1024 x 1024 image with its only strong pixel at one end"""
     n = 1024
