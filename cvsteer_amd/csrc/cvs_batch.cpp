@@ -25,16 +25,18 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <condition_variable>
 #include <mutex>
 #include <new>
 #include <string>
 #include <thread>
 #include <vector>
 
+#include "cvs_overlap.h"
 #include "cvsteer_hip.h"
 
 namespace {
+
+using cvs::shard_range;
 
 // ---------------------------------------------------------------------------------------------------- RCCL, lazily
 struct Rccl {
@@ -95,13 +97,6 @@ Rccl* rccl(std::string* why = nullptr)
     return r.so ? &r : nullptr;
 }
 
-// contiguous block [lo, hi) of `rank`: item f belongs to rank floor(f * world / n)
-void shard_range(int n, int world, int rank, int* lo, int* hi)
-{
-    *lo = (int)(((long long)rank * n + world - 1) / world);
-    *hi = (int)(((long long)(rank + 1) * n + world - 1) / world);
-}
-
 enum { TRANSPORT_NONE = 0, TRANSPORT_RCCL = 1, TRANSPORT_COPY = 2 };
 
 struct DevBuf {
@@ -148,11 +143,22 @@ int fail(cvs_batch b, int code, const std::string& what)
     return code;
 }
 
-#define B_HIP(b, expr)                                                                                   \
-    do {                                                                                                 \
-        hipError_t e__ = (expr);                                                                         \
-        if (e__ != hipSuccess) return fail(b, e__ == hipErrorOutOfMemory ? CVS_E_NOMEM : CVS_E_HIP,      \
-                                           std::string(#expr) + ": " + hipGetErrorString(e__));         \
+// (a rank thread of the host-plane path keeps its text to itself: the context's is set once the threads have joined)
+int fail(std::string& err, int code, const std::string& what)
+{
+    err = what;
+    return code;
+}
+
+// the one place a failed HIP call becomes a code and a text
+int hip_code(hipError_t e) { return e == hipErrorOutOfMemory ? CVS_E_NOMEM : CVS_E_HIP; }
+std::string hip_text(const char* what, hipError_t e) { return std::string(what) + ": " + hipGetErrorString(e); }
+
+// `to`: the batch, or a rank thread's own error string
+#define B_HIP(to, expr)                                                                \
+    do {                                                                               \
+        hipError_t e__ = (expr);                                                       \
+        if (e__ != hipSuccess) return fail(to, hip_code(e__), hip_text(#expr, e__));   \
     } while (0)
 
 #define B_NCCL(b, expr)                                                                                  \
@@ -234,7 +240,7 @@ struct GroupGuard {
     }
     void hip(hipError_t e, const char* what)
     {
-        if (e != hipSuccess) note(e == hipErrorOutOfMemory ? CVS_E_NOMEM : CVS_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
+        if (e != hipSuccess) note(hip_code(e), hip_text(what, e));
     }
     void nccl(ncclResult_t r, const char* what)
     {
@@ -379,17 +385,23 @@ int sync_all(cvs_batch b)
     return CVS_OK;
 }
 
+// the timing a call reports: the maximum over this process's ranks
+void fold_timing(cvs_batch_timing* t, double scatter, double compute, double gather)
+{
+    t->scatter_ms = std::max(t->scatter_ms, scatter);
+    t->compute_ms = std::max(t->compute_ms, compute);
+    t->gather_ms = std::max(t->gather_ms, gather);
+}
+
 void fill_timing(cvs_batch b, cvs_batch_timing* t)
 {
     if (!t) return;
-    t->scatter_ms = t->compute_ms = t->gather_ms = 0.0;
+    *t = cvs_batch_timing{0.0, 0.0, 0.0};
     for (Slot& s : b->slots) {
         float ms[3] = {0.f, 0.f, 0.f};
         (void)hipSetDevice(s.device);
         for (int i = 0; i < 3; ++i) (void)hipEventElapsedTime(&ms[i], s.ev[i], s.ev[i + 1]);
-        t->scatter_ms = std::max(t->scatter_ms, (double)ms[0]);
-        t->compute_ms = std::max(t->compute_ms, (double)ms[1]);
-        t->gather_ms = std::max(t->gather_ms, (double)ms[2]);
+        fold_timing(t, ms[0], ms[1], ms[2]);
     }
 }
 
@@ -406,6 +418,57 @@ bool host_plane(const cvs_plane* p, int rows, int cols, bool u8 = false)
            p->step >= (size_t)cols * (u8 ? 1 : sizeof(float));
 }
 
+// What one rank does in a cvs_batch_run, worked out once per call: its block [lo, lo + n) of the frames, and whether it reads the
+// caller's input planes / writes the caller's output planes directly (the root, unless its block is made to travel) or stages.
+struct Shard {
+    int lo, n;
+    bool in_place, out_in_place;
+};
+
+// plane i of a staging buffer of dense rows x cols planes lying back to back: f32, or (u8) bytes
+cvs_plane staged(const DevBuf& buf, size_t i, int rows, int cols, bool u8 = false)
+{
+    const size_t plane = (size_t)rows * cols;
+    if (u8) return cvs_plane{reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(buf.p) + i * plane), rows, cols, (size_t)cols, CVS_MEM_DEVICE | CVS_DEPTH_U8};
+    return cvs_plane{buf.p + i * plane, rows, cols, (size_t)cols * sizeof(float), CVS_MEM_DEVICE};
+}
+
+// what cvs_batch_local_result reports: the layout of `out` after this run (n = 0: an empty block, not the previous run's)
+void record_last(Slot& s, int n, int K, int rows, int cols, bool is_staged)
+{
+    s.last_n = n;
+    s.last_k = K;
+    s.last_rows = rows;
+    s.last_cols = cols;
+    s.last_staged = is_staged;
+}
+
+// Planes [first, first + count) of a staging buffer (rows x cols elements of esz bytes each, plane i at dev + i planes) to or from the
+// host planes host(i), queued on `stream`: planes that lie back to back on the host -- the usual [n][K][rows][cols] block -- travel as ONE
+// linear copy per run (a pitched 2-D copy of the same bytes runs at a third of the link rate), a plane with padded rows as a 2-D copy of
+// its own (cvs::walk_runs).  This decides whether the host link runs at full rate.
+template <class Host>
+hipError_t copy_planes(hipStream_t stream, hipMemcpyKind kind, void* dev, size_t esz, int rows, int cols, size_t first, size_t count, Host host)
+{
+    const size_t rowb = (size_t)cols * esz, plane = (size_t)rows * rowb;
+    const bool up = kind == hipMemcpyHostToDevice;
+    uint8_t* base = static_cast<uint8_t*>(dev) + first * plane;
+    hipError_t e = hipSuccess;
+    cvs::walk_runs(
+        count, plane, rowb, [&](size_t i) { return cvs::plane_at(host(first + i)); },
+        [&](size_t i, size_t run, uintptr_t addr) {
+            void *h = reinterpret_cast<void*>(addr), *d = base + i * plane;
+            e = hipMemcpyAsync(up ? d : h, up ? h : d, run * plane, kind, stream);
+            return e == hipSuccess;
+        },
+        [&](size_t i, uintptr_t addr, size_t step) {
+            void *h = reinterpret_cast<void*>(addr), *d = base + i * plane;
+            e = hipMemcpy2DAsync(up ? d : h, up ? rowb : step, up ? h : d, up ? step : rowb, rowb, rows, kind, stream);
+            return e == hipSuccess;
+        });
+    return e;
+}
+
 // Host planes (the reference's callers hold cv::Mat: example/steer.cpp:73-104).  Nothing goes through the root's GPU:
 // every rank pulls ITS frames from the caller's host planes over its own PCIe link and pushes its outputs back the
 // same way, all ranks at once.  Inside a rank the shard is cut into chunks of frames and three things overlap, as
@@ -416,6 +479,7 @@ struct HostRun {
     cvs_batch b;
     const cvs_batch_cfg* cfg;
     const cvs_plane *inputs, *outputs;
+    const Shard* plan;  // by rank
     int sel[8], K;
     bool u8;  // 8-bit input frames: bytes cross the link, the engine widens them on the device
     bool out8;  // 8-bit host output planes: the maps are normalised / converted on the device, bytes come back
@@ -425,191 +489,79 @@ int host_rank(const HostRun& R, Slot& s, std::string& err, double ms[3])
 {
     cvs_batch b = R.b;
     const int rows = R.cfg->rows, cols = R.cfg->cols, K = R.K;
-    const size_t plane = (size_t)rows * cols, rowb = (size_t)cols * sizeof(float);
-    int lo, hi;
-    shard_range(R.cfg->n_frames, b->world, s.rank, &lo, &hi);
-    const int n = hi - lo;
+    const int lo = R.plan[s.rank].lo, n = R.plan[s.rank].n;
     ms[0] = ms[1] = ms[2] = 0.0;
-    if (!n) {
-        s.last_n = 0;
-        s.last_staged = true;
-        return CVS_OK;
-    }
-#define H_TRY(expr)                                                                              \
-    do {                                                                                         \
-        hipError_t e__ = (expr);                                                                 \
-        if (e__ != hipSuccess) { err = std::string(#expr) + ": " + hipGetErrorString(e__); return e__ == hipErrorOutOfMemory ? CVS_E_NOMEM : CVS_E_HIP; } \
-    } while (0)
-    H_TRY(hipSetDevice(s.device));
+    record_last(s, n, K, rows, cols, true);
+    if (!n) return CVS_OK;
+    B_HIP(err, hipSetDevice(s.device));
     if (!s.up) {
-        H_TRY(hipStreamCreateWithFlags(&s.up, hipStreamNonBlocking));
-        H_TRY(hipStreamCreateWithFlags(&s.down, hipStreamNonBlocking));
+        B_HIP(err, hipStreamCreateWithFlags(&s.up, hipStreamNonBlocking));
+        B_HIP(err, hipStreamCreateWithFlags(&s.down, hipStreamNonBlocking));
     }
     int persist = 1;
     (void)cvs_get_option(s.h, CVS_OPT_PERSIST_STATE, &persist);
-    // with state kept, the handle's frames after the call must be the whole shard: one chunk
-    // Chunks GROW (round 6): the downloads set the pace (three maps down for one frame up) and run back to back once the first chunk's
-    // maps exist, so what the chunking costs is the time until then -- upload + launch of the FIRST chunk.  A thirty-second of the shard
-    // first, every later chunk twice its predecessor (its upload and launch hide behind the predecessor's download): 1 | 2 | 4 | 8 | 17 frames
-    // for a shard of 32 instead of four chunks of 8: 0.79 -> 0.84 of the link's roof for 8-bit frames in / three 8-bit maps out
-    // (profiles/r06_host_chunks.txt).
-    std::vector<int> c0(1, 0);
-    if (persist) c0.push_back(n);
-    else
-        for (int sz = std::max(1, n / 32); c0.back() < n; sz *= 2) c0.push_back((n - c0.back() <= sz + sz / 2 || c0.size() >= 5) ? n : c0.back() + sz);
+    // with state kept, the handle's frames after the call must be the whole shard: one chunk; otherwise chunks that grow (cvs::chunk_starts)
+    const std::vector<int> c0 = cvs::chunk_starts(n, persist != 0);
     const int nchunks = (int)c0.size() - 1;
     // the events are the slot's own (created once: a dozen hipEventCreate / Destroy per call were a tenth of a small batch's time)
     while ((int)s.host_ev.size() < 4 + 2 * nchunks) {
         hipEvent_t ev = nullptr;
-        H_TRY(s.host_ev.size() < 4 ? hipEventCreate(&ev) : hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        B_HIP(err, s.host_ev.size() < 4 ? hipEventCreate(&ev) : hipEventCreateWithFlags(&ev, hipEventDisableTiming));
         s.host_ev.push_back(ev);
     }
     hipEvent_t* t = s.host_ev.data();
     hipEvent_t* up_ev = s.host_ev.data() + 4;
     hipEvent_t* done_ev = s.host_ev.data() + 4 + nchunks;
-    // the download thread: chunk c may start once its launch has been queued (counter) and has finished (event)
-    std::mutex mu;
-    std::condition_variable cv;
-    int queued = 0;
-    bool stop = false;
+    // the download thread: chunk c may start once its launch has been queued (the gate) and has finished (event)
+    cvs::Gate gate;
     int drc = CVS_OK;
     std::string derr;
     std::thread down;
     if (R.cfg->gather) {
         down = std::thread([&]() {
             if (hipSetDevice(s.device) != hipSuccess) { drc = CVS_E_HIP; derr = "hipSetDevice"; return; }
-            for (int c = 0; c < nchunks; ++c) {
-                {
-                    std::unique_lock<std::mutex> lk(mu);
-                    cv.wait(lk, [&] { return queued > c || stop; });
-                    if (stop) return;
-                }
-                hipError_t e = hipStreamWaitEvent(s.down, done_ev[c], 0);
+            hipError_t e = hipSuccess;
+            for (int c = 0; c < nchunks && e == hipSuccess; ++c) {
+                if (!gate.wait(c)) return;
+                e = hipStreamWaitEvent(s.down, done_ev[c], 0);
                 if (c == 0 && e == hipSuccess) e = hipEventRecord(t[2], s.down);
-                if (R.out8) {
-                    // bytes: dense planes that lie back to back on the host (the usual [n][K][rows][cols] block) leave as
-                    // ONE linear copy per run -- a pitched 2-D copy of the same bytes runs at a third of the link rate
-                    const uint8_t* dev8 = reinterpret_cast<const uint8_t*>(s.out8.p);
-                    size_t first = (size_t)c0[c] * K, count = 0;
-                    uint8_t* run_dst = nullptr;
-                    auto flush = [&]() {
-                        if (count && e == hipSuccess) e = hipMemcpyAsync(run_dst, dev8 + first * plane, count * plane, hipMemcpyDeviceToHost, s.down);
-                        count = 0;
-                    };
-                    for (int i = c0[c]; e == hipSuccess && i < c0[c + 1]; ++i)
-                        for (int j = 0; e == hipSuccess && j < K; ++j) {
-                            const cvs_plane& o = R.outputs[(size_t)(lo + i) * 8 + R.sel[j]];
-                            uint8_t* dst = reinterpret_cast<uint8_t*>(o.data);
-                            const size_t idx = (size_t)i * K + j;
-                            if (o.step != (size_t)cols) {  // padded rows: a 2-D copy of this plane alone
-                                flush();
-                                if (e == hipSuccess) e = hipMemcpy2DAsync(dst, o.step, dev8 + idx * plane, (size_t)cols, (size_t)cols, rows, hipMemcpyDeviceToHost, s.down);
-                                continue;
-                            }
-                            if (count && dst == run_dst + count * plane) { ++count; continue; }
-                            flush();
-                            first = idx; run_dst = dst; count = 1;
-                        }
-                    flush();
-                } else {
-                    // f32 planes: the same -- dense planes that lie back to back leave as one linear copy per run
-                    size_t first = (size_t)c0[c] * K, count = 0;
-                    float* run_dst = nullptr;
-                    auto flush = [&]() {
-                        if (count && e == hipSuccess) e = hipMemcpyAsync(run_dst, s.out.p + first * plane, count * plane * sizeof(float), hipMemcpyDeviceToHost, s.down);
-                        count = 0;
-                    };
-                    for (int i = c0[c]; e == hipSuccess && i < c0[c + 1]; ++i)
-                        for (int j = 0; e == hipSuccess && j < K; ++j) {
-                            const cvs_plane& o = R.outputs[(size_t)(lo + i) * 8 + R.sel[j]];
-                            const size_t idx = (size_t)i * K + j;
-                            if (o.step != rowb) {
-                                flush();
-                                if (e == hipSuccess) e = hipMemcpy2DAsync(o.data, o.step, s.out.p + idx * plane, rowb, rowb, rows, hipMemcpyDeviceToHost, s.down);
-                                continue;
-                            }
-                            if (count && o.data == run_dst + count * plane) { ++count; continue; }
-                            flush();
-                            first = idx; run_dst = o.data; count = 1;
-                        }
-                    flush();
-                }
-                if (e != hipSuccess) { drc = CVS_E_HIP; derr = std::string("download: ") + hipGetErrorString(e); return; }
+                if (e == hipSuccess)
+                    e = copy_planes(s.down, hipMemcpyDeviceToHost, R.out8 ? s.out8.p : s.out.p, R.out8 ? 1 : sizeof(float), rows, cols, (size_t)c0[c] * K,
+                                    (size_t)(c0[c + 1] - c0[c]) * K, [&](size_t i) -> const cvs_plane& { return R.outputs[(lo + i / K) * 8 + R.sel[i % K]]; });
             }
-            hipError_t e = hipEventRecord(t[3], s.down);
+            if (e == hipSuccess) e = hipEventRecord(t[3], s.down);
             if (e == hipSuccess) e = hipStreamSynchronize(s.down);
-            if (e != hipSuccess) { drc = CVS_E_HIP; derr = std::string("download: ") + hipGetErrorString(e); }
+            if (e != hipSuccess) { drc = CVS_E_HIP; derr = hip_text("download", e); }
         });
     }
-    auto stop_down = [&](bool failed) {
-        if (down.joinable()) {
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                if (failed) stop = true;
-            }
-            cv.notify_all();
-            down.join();
-        }
-    };
     int rc = CVS_OK;
     hipError_t e = hipEventRecord(t[0], s.up);
     for (int c = 0; c < nchunks && e == hipSuccess && rc == CVS_OK; ++c) {
-        {
-            // dense frames that lie back to back on the host (one [n][rows][cols] block) go up as one linear copy per run
-            const size_t esz = R.u8 ? 1 : sizeof(float), frame_b = plane * esz;
-            uint8_t* dev = reinterpret_cast<uint8_t*>(s.in.p);
-            int first = c0[c], count = 0;
-            const uint8_t* run_src = nullptr;
-            auto flush = [&]() {
-                if (count && e == hipSuccess) e = hipMemcpyAsync(dev + (size_t)first * frame_b, run_src, (size_t)count * frame_b, hipMemcpyHostToDevice, s.up);
-                count = 0;
-            };
-            for (int i = c0[c]; e == hipSuccess && i < c0[c + 1]; ++i) {
-                const cvs_plane& im = R.inputs[lo + i];
-                const uint8_t* src = reinterpret_cast<const uint8_t*>(im.data);
-                if (im.step != (size_t)cols * esz) {
-                    flush();
-                    if (e == hipSuccess) e = hipMemcpy2DAsync(dev + (size_t)i * frame_b, (size_t)cols * esz, im.data, im.step, (size_t)cols * esz, rows, hipMemcpyHostToDevice, s.up);
-                    continue;
-                }
-                if (count && src == run_src + (size_t)count * frame_b) { ++count; continue; }
-                flush();
-                first = i; run_src = src; count = 1;
-            }
-            flush();
-        }
+        const int cn = c0[c + 1] - c0[c];
+        e = copy_planes(s.up, hipMemcpyHostToDevice, s.in.p, R.u8 ? 1 : sizeof(float), rows, cols, c0[c], cn,
+                        [&](size_t i) -> const cvs_plane& { return R.inputs[lo + i]; });
         if (e == hipSuccess) e = hipEventRecord(up_ev[c], s.up);
         if (e == hipSuccess && c == nchunks - 1) e = hipEventRecord(t[1], s.up);
         if (e == hipSuccess) e = hipStreamWaitEvent(s.stream, up_ev[c], 0);
         if (e != hipSuccess) break;
-        const int cn = c0[c + 1] - c0[c];
         std::vector<cvs_plane> im(cn), ou((size_t)cn * 8);
         std::memset(ou.data(), 0, ou.size() * sizeof(cvs_plane));
         for (int i = 0; i < cn; ++i) {
-            if (R.u8) im[i] = cvs_plane{reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(s.in.p) + (size_t)(c0[c] + i) * plane), rows, cols, (size_t)cols, CVS_MEM_DEVICE | CVS_DEPTH_U8};
-            else im[i] = cvs_plane{s.in.p + (size_t)(c0[c] + i) * plane, rows, cols, rowb, CVS_MEM_DEVICE};
+            im[i] = staged(s.in, c0[c] + i, rows, cols, R.u8);
             // 8-bit outputs: the chunk's byte planes themselves -- the pipeline launch quantises (gain) or reduces min / max for one
             // quantise launch (normalise) behind it; no f32 maps of the chunk are staged here
-            for (int j = 0; j < K; ++j)
-                ou[(size_t)i * 8 + R.sel[j]] = R.out8 ? cvs_plane{reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(s.out8.p) + ((size_t)(c0[c] + i) * K + j) * plane),
-                                                                   rows, cols, (size_t)cols, CVS_MEM_DEVICE | CVS_DEPTH_U8}
-                                                      : cvs_plane{s.out.p + ((size_t)(c0[c] + i) * K + j) * plane, rows, cols, rowb, CVS_MEM_DEVICE};
+            for (int j = 0; j < K; ++j) ou[(size_t)i * 8 + R.sel[j]] = staged(R.out8 ? s.out8 : s.out, (size_t)(c0[c] + i) * K + j, rows, cols, R.out8);
         }
         if (R.out8 && (rc = cvs_set_u8_gain(s.h, b->u8_gain)) != CVS_OK) { err = std::string("cvs_set_u8_gain: ") + cvs_last_error(s.h); break; }
         rc = cvs_pipeline_batch(s.h, im.data(), cn, ou.data());
         if (rc != CVS_OK) { err = std::string("cvs_pipeline_batch: ") + cvs_last_error(s.h); break; }
         e = hipEventRecord(done_ev[c], s.stream);
-        if (e == hipSuccess) {
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                queued = c + 1;
-            }
-            cv.notify_all();
-        }
+        if (e == hipSuccess) gate.publish(c + 1);
     }
     const bool failed = e != hipSuccess || rc != CVS_OK;
-    if (e != hipSuccess) { err = std::string("upload: ") + hipGetErrorString(e); rc = CVS_E_HIP; }
-    stop_down(failed);
+    if (e != hipSuccess) { err = hip_text("upload", e); rc = CVS_E_HIP; }
+    if (failed) gate.stop();   // before the join: the download thread may be waiting for a chunk that will never be queued
+    if (down.joinable()) down.join();
     if (!failed && drc != CVS_OK) { rc = drc; err = derr; }
     if (rc == CVS_OK) {
         e = hipStreamSynchronize(s.stream);
@@ -628,21 +580,14 @@ int host_rank(const HostRun& R, Slot& s, std::string& err, double ms[3])
     } else {
         (void)hipDeviceSynchronize();
     }
-    s.last_n = n;
-    s.last_k = K;
-    s.last_rows = rows;
-    s.last_cols = cols;
-    s.last_staged = true;
-#undef H_TRY
     return rc;
 }
 
+// (every rank is in this process: cvs_batch_run checked that before the ranks agreed)
 int run_host(cvs_batch b, const cvs_batch_cfg* cfg, const cvs_plane* inputs, const cvs_plane* outputs, const int* sel, int K,
-             cvs_batch_timing* timing)
+             const std::vector<Shard>& plan, cvs_batch_timing* timing)
 {
     const int rows = cfg->rows, cols = cfg->cols, F = cfg->n_frames;
-    if ((int)b->slots.size() != b->world)
-        return fail(b, CVS_E_UNSUPPORTED, "host planes need every rank in the calling process (each GPU pulls its frames over its own link)");
     const bool u8 = (inputs[0].mem & CVS_DEPTH_U8) != 0;
     // host outputs may be 8-bit planes too (what the example writes, steer.cpp:92-122): the maps are then normalised /
     // converted on the device chunk by chunk and only bytes come back, overlapped with the uploads and launches of the next chunk
@@ -656,14 +601,12 @@ int run_host(cvs_batch b, const cvs_batch_cfg* cfg, const cvs_plane* inputs, con
     const size_t plane = (size_t)rows * cols;
     int rc;
     for (Slot& s : b->slots) {
-        int lo, hi;
-        shard_range(F, b->world, s.rank, &lo, &hi);
-        const size_t n = (size_t)(hi - lo);
+        const size_t n = (size_t)plan[s.rank].n;
         if (n && (rc = reserve(b, s, s.in, n * plane))) return rc;
         if (n && !out8 && (rc = reserve(b, s, s.out, n * K * plane))) return rc;   // (8-bit outputs: the bytes only)
         if (n && out8 && (rc = reserve(b, s, s.out8, (n * K * plane + 3) / 4 + 64))) return rc;
     }
-    HostRun R{b, cfg, inputs, outputs, {0}, K, u8, out8};
+    HostRun R{b, cfg, inputs, outputs, plan.data(), {0}, K, u8, out8};
     for (int j = 0; j < K; ++j) R.sel[j] = sel[j];
     const size_t nl = b->slots.size();
     std::vector<int> rcs(nl, CVS_OK);
@@ -676,27 +619,31 @@ int run_host(cvs_batch b, const cvs_batch_cfg* cfg, const cvs_plane* inputs, con
     for (size_t i = 0; i < nl; ++i)
         if (rcs[i] != CVS_OK) return fail(b, rcs[i], "rank " + std::to_string(b->slots[i].rank) + ": " + errs[i]);
     if (timing) {
-        timing->scatter_ms = timing->compute_ms = timing->gather_ms = 0.0;
-        for (size_t i = 0; i < nl; ++i) {
-            timing->scatter_ms = std::max(timing->scatter_ms, ms[i * 3]);
-            timing->compute_ms = std::max(timing->compute_ms, ms[i * 3 + 1]);
-            timing->gather_ms = std::max(timing->gather_ms, ms[i * 3 + 2]);
-        }
+        *timing = cvs_batch_timing{0.0, 0.0, 0.0};
+        for (size_t i = 0; i < nl; ++i) fold_timing(timing, ms[i * 3], ms[i * 3 + 1], ms[i * 3 + 2]);
     }
     return CVS_OK;
 }
 
-int create_common(int kind, int width, float spacing, cvs_batch* out, cvs_batch* made)
+// Both create calls: the arguments (args_ok: what only the caller can check) and the devices the call names are checked BEFORE the
+// context exists, so nothing has to be taken down again; then *out = the context with `world` set and one empty slot per device.
+int create_checked(int kind, int width, float spacing, bool args_ok, const int* devices, int ndev, int world, cvs_batch* out)
 {
     if (!out) return CVS_E_BADARG;
     *out = nullptr;
-    if (cvs_num_basis(kind) == 0 || width < 1) return CVS_E_BADARG;
+    if (cvs_num_basis(kind) == 0 || width < 1 || !args_ok) return CVS_E_BADARG;
+    int have = 0;
+    if (hipGetDeviceCount(&have) != hipSuccess || have <= 0) return CVS_E_HIP;  // no CPU fallback
+    for (int i = 0; i < ndev; ++i)
+        if (devices[i] < 0 || devices[i] >= have) return CVS_E_BADARG;
     cvs_batch b = new (std::nothrow) cvs_batch_context();
     if (!b) return CVS_E_NOMEM;
     b->kind = kind;
     b->width = width;
     b->spacing = spacing;
-    *made = b;
+    b->world = world;
+    b->slots.resize(ndev);
+    *out = b;
     return CVS_OK;
 }
 
@@ -706,23 +653,15 @@ extern "C" {
 
 int cvs_batch_create_local(int kind, int width, float spacing, int ndev, const int* devices, cvs_batch* out)
 {
-    cvs_batch b = nullptr;
-    int rc = create_common(kind, width, spacing, out, &b);
+    int rc = create_checked(kind, width, spacing, ndev >= 1 && devices, devices, ndev, ndev, out);
     if (rc) return rc;
-    if (ndev < 1 || !devices) { delete b; return CVS_E_BADARG; }
-    int have = 0;
-    if (hipGetDeviceCount(&have) != hipSuccess || have <= 0) { delete b; return CVS_E_HIP; }  // no CPU fallback
+    cvs_batch b = *out;   // from here on the caller reads the error, then destroys
     bool dup = false;
     for (int i = 0; i < ndev; ++i) {
-        if (devices[i] < 0 || devices[i] >= have) { delete b; return CVS_E_BADARG; }
         for (int j = 0; j < i; ++j) dup = dup || devices[j] == devices[i];
-    }
-    b->world = ndev;
-    b->slots.resize(ndev);
-    for (int i = 0; i < ndev; ++i) {
         b->slots[i].rank = i;
         b->slots[i].device = devices[i];
-        if ((rc = init_slot(b, b->slots[i]))) { *out = b; return rc; }  // caller reads the error, then destroys
+        if ((rc = init_slot(b, b->slots[i]))) return rc;
     }
     if (dup) {
         b->transport = TRANSPORT_COPY;   // rehearsal: several ranks on one device
@@ -731,16 +670,15 @@ int cvs_batch_create_local(int kind, int width, float spacing, int ndev, const i
         Rccl* R = rccl(&why);
         if (!R) {
             if (ndev == 1) b->transport = TRANSPORT_NONE;  // one rank needs no transport at all
-            else { *out = b; return fail(b, CVS_E_HIP, "RCCL is not available: " + why); }
+            else return fail(b, CVS_E_HIP, "RCCL is not available: " + why);
         } else {
             std::vector<ncclComm_t> comms(ndev);
             ncclResult_t r = R->CommInitAll(comms.data(), ndev, devices);
-            if (r != ncclSuccess) { *out = b; return fail(b, CVS_E_HIP, std::string("ncclCommInitAll: ") + R->GetErrorString(r)); }
+            if (r != ncclSuccess) return fail(b, CVS_E_HIP, std::string("ncclCommInitAll: ") + R->GetErrorString(r));
             for (int i = 0; i < ndev; ++i) b->slots[i].comm = comms[i];
             b->transport = TRANSPORT_RCCL;
         }
     }
-    *out = b;
     return CVS_OK;
 }
 
@@ -758,18 +696,11 @@ int cvs_batch_unique_id(void* id128)
 
 int cvs_batch_create_rank(int kind, int width, float spacing, const void* id128, int world, int rank, int device, cvs_batch* out)
 {
-    cvs_batch b = nullptr;
-    int rc = create_common(kind, width, spacing, out, &b);
+    int rc = create_checked(kind, width, spacing, id128 && world >= 1 && rank >= 0 && rank < world, &device, 1, world, out);
     if (rc) return rc;
-    if (!id128 || world < 1 || rank < 0 || rank >= world) { delete b; return CVS_E_BADARG; }
-    int have = 0;
-    if (hipGetDeviceCount(&have) != hipSuccess || have <= 0) { delete b; return CVS_E_HIP; }
-    if (device < 0 || device >= have) { delete b; return CVS_E_BADARG; }
-    b->world = world;
-    b->slots.resize(1);
+    cvs_batch b = *out;
     b->slots[0].rank = rank;
     b->slots[0].device = device;
-    *out = b;
     if ((rc = init_slot(b, b->slots[0]))) return rc;
     std::string why;
     Rccl* R = rccl(&why);
@@ -850,6 +781,13 @@ int cvs_batch_run(cvs_batch b, const cvs_batch_cfg* cfg, const cvs_plane* inputs
     Slot* rs = local(b, root);
     const bool via = cfg->self_via_transport != 0 && b->transport != TRANSPORT_NONE;
     if (b->world > 1 && b->transport == TRANSPORT_NONE) return fail(b, CVS_E_HIP, "no transport");
+    // the root writes its own shard straight into the caller's planes when it gathers; everybody else stages
+    std::vector<Shard> plan(b->world);
+    for (int r = 0; r < b->world; ++r) {
+        int lo, hi;
+        shard_range(F, b->world, r, &lo, &hi);
+        plan[r] = Shard{lo, hi - lo, r == root && !via, r == root && !via && cfg->gather};
+    }
     // What only THIS process can know -- are the root's planes usable, do the staging buffers fit -- is collected into
     // local_rc without returning, and the ranks agree on it before anybody queues a message (see agree()): a rank that
     // returned early here would leave its peers inside ncclRecv for ever.
@@ -880,73 +818,52 @@ int cvs_batch_run(cvs_batch b, const cvs_batch_cfg* cfg, const cvs_plane* inputs
     // staging on every local rank that does not work in place
     for (Slot& s : b->slots) {
         if (local_rc != CVS_OK || host) break;
-        int lo, hi;
-        shard_range(F, b->world, s.rank, &lo, &hi);
-        const size_t n = (size_t)(hi - lo);
-        const bool in_place = s.rank == root && !via;
-        if (!in_place && n && (rc = reserve(b, s, s.in, n * plane))) { local_rc = rc; break; }
-        // the root writes its own shard straight into the caller's planes when it gathers; everybody else stages
-        const bool out_in_place = s.rank == root && cfg->gather && !via;
-        if (!out_in_place && n && (rc = reserve(b, s, s.out, n * K * plane))) { local_rc = rc; break; }
+        const Shard& sh = plan[s.rank];
+        const size_t n = (size_t)sh.n;
+        if (!sh.in_place && n && (rc = reserve(b, s, s.in, n * plane))) { local_rc = rc; break; }
+        if (!sh.out_in_place && n && (rc = reserve(b, s, s.out, n * K * plane))) { local_rc = rc; break; }
     }
     if ((rc = agree(b, local_rc, hash_ints({rows, cols, F, (long long)cfg->outputs, root, cfg->gather, cfg->self_via_transport, 4}))))
         return rc;
-    if (host) return run_host(b, cfg, inputs, outputs, sel, K, timing);   // every rank is in this process (checked above)
+    if (host) return run_host(b, cfg, inputs, outputs, sel, K, plan, timing);   // every rank is in this process (checked above)
     if ((rc = record_all(b, 0))) return rc;
     // ---- scatter: root -> ranks, frame by frame (a frame is one contiguous message) ----
     {
         std::vector<Move> mv;
         for (int r = 0; r < b->world; ++r) {
-            if (r == root && !via) continue;
-            int lo, hi;
-            shard_range(F, b->world, r, &lo, &hi);
+            if (plan[r].in_place) continue;
             Slot* d = local(b, r);
-            for (int f = lo; f < hi; ++f)
-                mv.push_back({root, r, rs ? inputs[f].data : nullptr, d ? d->in.p + (size_t)(f - lo) * plane : nullptr, plane});
+            for (int i = 0; i < plan[r].n; ++i)
+                mv.push_back({root, r, rs ? inputs[plan[r].lo + i].data : nullptr, d ? d->in.p + (size_t)i * plane : nullptr, plane});
         }
         if ((rc = run_moves(b, mv))) return rc;
     }
     if ((rc = record_all(b, 1))) return rc;
     // ---- compute: the fused pipeline on every local rank's block, one launch per rank ----
     for (Slot& s : b->slots) {
-        int lo, hi;
-        shard_range(F, b->world, s.rank, &lo, &hi);
-        const int n = hi - lo;
-        if (!n) {
-            s.last_n = 0;  // cvs_batch_local_result: an empty block, not the previous run's
-            s.last_staged = true;
-            continue;
-        }
-        const bool in_place = s.rank == root && !via;
-        const bool out_in_place = s.rank == root && cfg->gather && !via;
+        const Shard& sh = plan[s.rank];
+        const int lo = sh.lo, n = sh.n;
+        record_last(s, n, K, rows, cols, !n || !sh.out_in_place);
+        if (!n) continue;
         std::vector<cvs_plane> im(n), ou((size_t)n * 8);
         std::memset(ou.data(), 0, ou.size() * sizeof(cvs_plane));
         for (int i = 0; i < n; ++i) {
-            im[i] = in_place ? inputs[lo + i] : cvs_plane{s.in.p + (size_t)i * plane, rows, cols, (size_t)cols * sizeof(float), CVS_MEM_DEVICE};
-            for (int j = 0; j < K; ++j)
-                ou[(size_t)i * 8 + sel[j]] = out_in_place ? outputs[(size_t)(lo + i) * 8 + sel[j]]
-                                                          : cvs_plane{s.out.p + ((size_t)i * K + j) * plane, rows, cols, (size_t)cols * sizeof(float), CVS_MEM_DEVICE};
+            im[i] = sh.in_place ? inputs[lo + i] : staged(s.in, i, rows, cols);
+            for (int j = 0; j < K; ++j) ou[(size_t)i * 8 + sel[j]] = sh.out_in_place ? outputs[(size_t)(lo + i) * 8 + sel[j]] : staged(s.out, (size_t)i * K + j, rows, cols);
         }
         B_CVS(b, s.h, cvs_pipeline_batch(s.h, im.data(), n, ou.data()));
-        s.last_n = n;
-        s.last_k = K;
-        s.last_rows = rows;
-        s.last_cols = cols;
-        s.last_staged = !out_in_place;
     }
     if ((rc = record_all(b, 2))) return rc;
     // ---- gather: ranks -> root, plane by plane ----
     if (cfg->gather) {
         std::vector<Move> mv;
         for (int r = 0; r < b->world; ++r) {
-            if (r == root && !via) continue;
-            int lo, hi;
-            shard_range(F, b->world, r, &lo, &hi);
+            if (plan[r].in_place) continue;
             Slot* s = local(b, r);
-            for (int f = lo; f < hi; ++f)
+            for (int i = 0; i < plan[r].n; ++i)
                 for (int j = 0; j < K; ++j)
-                    mv.push_back({r, root, s ? s->out.p + ((size_t)(f - lo) * K + j) * plane : nullptr,
-                                  rs ? outputs[(size_t)f * 8 + sel[j]].data : nullptr, plane});
+                    mv.push_back({r, root, s ? s->out.p + ((size_t)i * K + j) * plane : nullptr,
+                                  rs ? outputs[(size_t)(plan[r].lo + i) * 8 + sel[j]].data : nullptr, plane});
         }
         if ((rc = run_moves(b, mv))) return rc;
     }
@@ -1028,9 +945,8 @@ int cvs_batch_pyramid_setup(cvs_batch b, const cvs_plane* image, int rows, int c
             for (Slot& s : b->slots) {
                 if (!g.ok()) break;
                 g.hip(hipSetDevice(s.device), "hipSetDevice");
-                const float* src = s.rank == root ? image->data : s.image.p;
-                float* dst = s.rank == root ? image->data : s.image.p;
-                if (g.ok()) g.nccl(g.R->Broadcast(src, dst, plane0, ncclFloat, root, s.comm, s.stream), "ncclBroadcast");
+                float* buf = s.rank == root ? image->data : s.image.p;   // in place on every rank
+                if (g.ok()) g.nccl(g.R->Broadcast(buf, buf, plane0, ncclFloat, root, s.comm, s.stream), "ncclBroadcast");
             }
             if ((rc = g.end(b))) return rc;
         } else {

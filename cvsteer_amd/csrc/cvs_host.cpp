@@ -2,24 +2,11 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
-#include <atomic>
-#include <chrono>
-#include <condition_variable>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <limits>
-#include <map>
-#include <mutex>
-#include <set>
-#include <tuple>
-#include <new>
-#include <string>
 #include <thread>
 #include <vector>
 
 #include "cvs_context.h"
+#include "cvs_overlap.h"
 
 namespace cvs {
 
@@ -59,10 +46,7 @@ int host_pipeline(cvs_handle h, Call& c, BasisArgs& a, float* scr)
     note_launch(h, a);
 
     // download thread: band b's outputs leave as soon as its kernel has finished
-    std::mutex mu;
-    std::condition_variable cv;
-    int enqueued = 0;
-    bool abort_dl = false;
+    Gate gate;
     hipError_t dl_err = hipSuccess;
     const std::vector<Pending> outs = c.outs;
     const int rows = a.rows, device = h->device;
@@ -72,20 +56,12 @@ int host_pipeline(cvs_handle h, Call& c, BasisArgs& a, float* scr)
         downloader = std::thread([&, rows, device, s_down, per, nbands] {
             hipError_t e = hipSetDevice(device);
             for (int b = 0; b < nbands && e == hipSuccess; ++b) {
-                {
-                    std::unique_lock<std::mutex> lock(mu);
-                    cv.wait(lock, [&] { return enqueued > b || abort_dl; });
-                    if (abort_dl) break;
-                }
+                if (!gate.wait(b)) break;
                 const int lo = b * per, hi = std::min(rows, lo + per);
                 e = hipStreamWaitEvent(s_down, comp[b], 0);
                 for (const Pending& o : outs) {
                     if (e != hipSuccess) break;
-                    if (o.host->step == o.pitch * sizeof(float) && o.host->step == (size_t)o.host->cols * sizeof(float)) {  // dense on both sides
-                        e = hipMemcpyAsync(reinterpret_cast<char*>(o.host->data) + (size_t)lo * o.host->step, o.dev + (size_t)lo * o.pitch,
-                                           (size_t)(hi - lo) * o.host->step, hipMemcpyDeviceToHost, s_down);
-                        continue;
-                    }
+                    // (dense on both sides: copy_rows makes it one linear copy)
                     e = copy_rows(reinterpret_cast<char*>(o.host->data) + (size_t)lo * o.host->step, o.host->step, o.dev + (size_t)lo * o.pitch,
                                          o.pitch * sizeof(float), (size_t)o.host->cols * sizeof(float), hi - lo, hipMemcpyDeviceToHost, s_down);
                 }
@@ -94,18 +70,10 @@ int host_pipeline(cvs_handle h, Call& c, BasisArgs& a, float* scr)
             dl_err = e;
         });
     }
-    auto stop = [&](int rc) {
-        {
-            std::lock_guard<std::mutex> lock(mu);
-            abort_dl = true;
-        }
-        cv.notify_all();
-        if (downloader.joinable()) downloader.join();
-        return rc;
-    };
     const cvs_plane* img = c.deferred_image;  // nullptr: the image is already on the device, only outputs travel
     int up_to = 0;                            // rows of the image uploaded so far
-    for (int b = 0; b < nbands; ++b) {
+    int rc = CVS_OK;
+    for (int b = 0; b < nbands && rc == CVS_OK; ++b) {
         const int lo = b * per, hi = std::min(a.rows, lo + per);
         if (img) {
             const int need = std::min(a.rows, hi + W);  // the band's kernel reads W rows beyond its last output row
@@ -123,26 +91,24 @@ int host_pipeline(cvs_handle h, Call& c, BasisArgs& a, float* scr)
                                          reinterpret_cast<const char*>(img->data) + (size_t)up_to * img->step, img->step, (size_t)img->cols * sizeof(float),
                                          need - up_to, hipMemcpyHostToDevice, h->s_up);
                 }
-                if (e != hipSuccess) return stop(fail_hip(h, e, "host pipeline upload"));
+                if (e != hipSuccess) { rc = fail_hip(h, e, "host pipeline upload"); break; }
                 up_to = need;
             }
             hipError_t e = hipEventRecord(up[b], h->s_up);
             if (e == hipSuccess) e = hipStreamWaitEvent(h->stream, up[b], 0);
-            if (e != hipSuccess) return stop(fail_hip(h, e, "host pipeline ordering"));
+            if (e != hipSuccess) { rc = fail_hip(h, e, "host pipeline ordering"); break; }
         }
         BasisArgs ab = a;
         ab.out_row_lo = lo;
         ab.out_row_hi = hi;
         hipError_t e = launch_basis(h->kind, h->width, h->taps, ab, scr, h->stream);
         if (e == hipSuccess) e = hipEventRecord(comp[b], h->stream);
-        if (e != hipSuccess) return stop(fail_hip(h, e, "host pipeline launch"));
-        {
-            std::lock_guard<std::mutex> lock(mu);
-            enqueued = b + 1;
-        }
-        cv.notify_all();
+        if (e != hipSuccess) rc = fail_hip(h, e, "host pipeline launch");
+        else gate.publish(b + 1);
     }
+    if (rc != CVS_OK) gate.stop();   // before the join: the downloader may be waiting for a band that will never be queued
     if (downloader.joinable()) downloader.join();
+    if (rc != CVS_OK) return rc;
     if (dl_err != hipSuccess) return fail_hip(h, dl_err, "host pipeline download");
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     c.outs.clear();  // nothing left for finish() to copy

@@ -3,20 +3,26 @@
 // a byte-for-byte model on random views; find_overlap, the contour tail's sorted check, against the plain loop over planes_overlap), the
 // CVS_OPTS parser on hostile strings, the state layout arithmetic (layout_state on
 // every kind / size / grouping: offsets inside the block, no two planes sharing an element), the plane-run and one-resource classifier
-// of cvs_layout.h (a table of layouts with the answer every call site gave before it existed) and the tap generator.  A cvs_context is
-// a plain struct: it is built here without a HIP call; no entry point that touches the device is called.
+// of cvs_layout.h (a table of layouts with the answer every call site gave before it existed), what the overlapped host paths share
+// (cvs_overlap.h: the run walker against a plane-by-plane copy on random layouts, the chunk schedule, the shard blocks, the worker gate
+// between two threads) and the tap generator.  A cvs_context is a plain struct: it is built here without a HIP call; no entry point
+// that touches the device is called.
 // Built and run by tools/run_sanitizers.sh and tests/test_sanitizers_cpu.py:
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude -Icvsteer_amd/csrc -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include \
 //       tests/cpp/host_logic_san.cpp cvsteer_amd/csrc/{cvs_handle,cvs_tune,cvs_state,cvs_taps}.cpp -L/opt/rocm/lib -lamdhip64 -lpthread
+#include <atomic>
+#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <set>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "cvs_context.h"
 #include "cvs_layout.h"
+#include "cvs_overlap.h"
 
 namespace cvs {
 // the two kernel-side symbols the host objects refer to (never reached here)
@@ -39,6 +45,237 @@ static unsigned rnd()
             return 1;                                                       \
         }                                                                   \
     } while (0)
+
+// ---- cvs_overlap.h: the run walker against a plane-by-plane, row-by-row copy ----
+// The host copies of the batch layer on memcpy: a "device" arena holds n = frames x K planes back to back, a "host" arena holds them where
+// the draw put them -- right behind each other, behind a hole, with padded rows, in descending order, frame by frame descending -- and is
+// reached as cvs_batch.cpp reaches it, through a table of eight planes per frame.  Both directions, 1- and 4-byte elements.  The arenas are
+// heap blocks of exactly the size in use (ASan sees a copy that leaves them) and carry a marker wherever no plane lies.
+static int check_walk_runs()
+{
+    using namespace cvs;
+    const unsigned char kMark = 0xa5;
+    int long_runs = 0, across_frames = 0, padded_planes = 0, descending = 0;
+    for (int it = 0; it < 6000; ++it) {
+        const size_t esz = rnd() & 1 ? 4 : 1;
+        const int rows = 1 + rnd() % 4, cols = 1 + rnd() % 6, K = 1 + rnd() % 3, frames = 1 + rnd() % 5;
+        const size_t n = (size_t)K * frames, rowb = cols * esz, plane = rows * rowb;
+        const bool up = rnd() & 1;
+        // n places in ascending address order; the next place starts where this one ends unless a hole is drawn in front of it
+        struct Place { size_t off, step; };
+        std::vector<Place> place(n);
+        size_t cur = 16;
+        for (Place& p : place) {
+            const unsigned kind = rnd() % 8;
+            if (kind == 0) cur += esz * (1 + rnd() % 9);
+            p = {cur, rowb + (kind == 1 || kind == 2 ? esz * (1 + rnd() % 3) : 0)};
+            cur += rows * p.step;
+        }
+        std::vector<unsigned char> host(cur + 16), dev(16 + n * plane + 16);
+        // which place plane i takes: in order, all descending, or the frames descending with each frame's planes in order
+        const unsigned mode = rnd() % 4;
+        int sel[3];
+        for (int j = 0; j < K; ++j) sel[j] = 2 * j + (rnd() & 1);
+        std::vector<PlaneAt> table((size_t)frames * 8, PlaneAt{0, 0});
+        for (size_t i = 0; i < n; ++i) {
+            const Place& p = place[mode == 2 ? n - 1 - i : mode == 3 ? (frames - 1 - i / K) * K + i % K : i];
+            table[i / K * 8 + sel[i % K]] = {reinterpret_cast<uintptr_t>(host.data()) + p.off, p.step};
+        }
+        auto at = [&](size_t i) { return table[i / K * 8 + sel[i % K]]; };
+        for (unsigned char& b : (up ? host : dev)) b = (unsigned char)rnd();
+        for (unsigned char& b : (up ? dev : host)) b = kMark;
+        // the model: every plane on its own, row by row
+        std::vector<unsigned char> want_host = host, want_dev = dev;
+        for (size_t i = 0; i < n; ++i)
+            for (int r = 0; r < rows; ++r) {
+                const size_t h = at(i).addr - reinterpret_cast<uintptr_t>(host.data()) + r * at(i).step, d = 16 + i * plane + r * rowb;
+                if (up) std::memcpy(&want_dev[d], &host[h], rowb);
+                else std::memcpy(&want_host[h], &dev[d], rowb);
+            }
+        // the maximal runs of dense planes lying back to back, counted on their own
+        size_t runs = 0, pitched_want = 0;
+        for (size_t i = 0; i < n; ++i) {
+            if (at(i).step != rowb) ++pitched_want;
+            else if (i == 0 || at(i - 1).step != rowb || at(i).addr != at(i - 1).addr + plane) ++runs;
+        }
+        size_t linear_calls = 0, pitched_calls = 0, linear_planes = 0;
+        unsigned char* staged = dev.data() + 16;
+        const bool done = walk_runs(
+            n, plane, rowb, at,
+            [&](size_t first, size_t count, uintptr_t addr) {
+                ++linear_calls;
+                linear_planes += count;
+                long_runs += count > 1;
+                across_frames += first / K != (first + count - 1) / K;
+                if (up) std::memcpy(staged + first * plane, reinterpret_cast<void*>(addr), count * plane);
+                else std::memcpy(reinterpret_cast<void*>(addr), staged + first * plane, count * plane);
+                return true;
+            },
+            [&](size_t i, uintptr_t addr, size_t step) {
+                ++pitched_calls;
+                for (int r = 0; r < rows; ++r) {
+                    if (up) std::memcpy(staged + i * plane + r * rowb, reinterpret_cast<void*>(addr + r * step), rowb);
+                    else std::memcpy(reinterpret_cast<void*>(addr + r * step), staged + i * plane + r * rowb, rowb);
+                }
+                return true;
+            });
+        REQUIRE(done);
+        REQUIRE(host == want_host && dev == want_dev);   // the planes, and every marker byte around and between them
+        REQUIRE(linear_calls == runs && pitched_calls == pitched_want && linear_planes + pitched_calls == n);
+        padded_planes += (int)pitched_want;
+        descending += mode >= 2 && frames > 1;
+    }
+    REQUIRE(long_runs > 1500 && across_frames > 500 && padded_planes > 3000 && descending > 1500);   // (the generator reaches every case)
+
+    // fixed layouts on made-up addresses: the calls themselves
+    struct Call {
+        char what;
+        size_t i, count;
+        uintptr_t addr;
+        size_t step;
+        bool operator==(const Call& o) const { return what == o.what && i == o.i && count == o.count && addr == o.addr && step == o.step; }
+    };
+    const size_t rowb = 64, plane = 4 * rowb, pstep = 80, pplane = 4 * pstep;
+    const uintptr_t base = 0x40000000u;
+    bool ok = false;
+    auto calls = [&](const std::vector<PlaneAt>& planes, size_t fail_at = 0) {
+        std::vector<Call> log;
+        ok = walk_runs(
+            planes.size(), plane, rowb, [&](size_t i) { return planes[i]; },
+            [&](size_t first, size_t count, uintptr_t addr) { log.push_back({'L', first, count, addr, 0}); return log.size() != fail_at; },
+            [&](size_t i, uintptr_t addr, size_t step) { log.push_back({'P', i, 1, addr, step}); return log.size() != fail_at; });
+        return log;
+    };
+    typedef std::vector<Call> Log;
+    std::vector<PlaneAt> dense5, padded5;
+    for (size_t i = 0; i < 5; ++i) {
+        dense5.push_back({base + i * plane, rowb});
+        padded5.push_back({base + i * pplane, pstep});
+    }
+    REQUIRE(calls(dense5) == (Log{{'L', 0, 5, base, 0}}) && ok);                                    // all dense: one call
+    Log all_padded = calls(padded5);
+    REQUIRE(ok && all_padded.size() == 5);                                                           // all padded: no linear call
+    for (size_t i = 0; i < 5; ++i) REQUIRE(all_padded[i] == (Call{'P', i, 1, base + i * pplane, pstep}));
+    REQUIRE(calls({{base, rowb}}) == (Log{{'L', 0, 1, base, 0}}) && ok);                            // a single plane
+    REQUIRE(calls({{base, pstep}}) == (Log{{'P', 0, 1, base, pstep}}) && ok);
+    REQUIRE(calls({}).empty() && ok);
+    // a dense plane right in front of a padded one and right behind it: three calls, in order
+    REQUIRE(calls({{base, rowb}, {base + plane, pstep}, {base + plane + pplane, rowb}}) ==
+            (Log{{'L', 0, 1, base, 0}, {'P', 1, 1, base + plane, pstep}, {'L', 2, 1, base + plane + pplane, 0}}) && ok);
+    // a padded plane ends the run for good: the dense plane behind it does not join it, even where its address continues it
+    REQUIRE(calls({{base, rowb}, {base + 16 * plane, pstep}, {base + plane, rowb}}) ==
+            (Log{{'L', 0, 1, base, 0}, {'P', 1, 1, base + 16 * plane, pstep}, {'L', 2, 1, base + plane, 0}}) && ok);
+    // two planes that are the same plane, and a step back by one plane: no run
+    REQUIRE(calls({{base, rowb}, {base, rowb}, {base - plane, rowb}}).size() == 3 && ok);
+    // a callback that fails: false, and nothing is called after it -- L(0,2) P(2) L(3,2) P(5) is the whole walk
+    const std::vector<PlaneAt> mixed = {{base, rowb}, {base + plane, rowb}, {base + 8 * plane, pstep}, {base + 20 * plane, rowb}, {base + 21 * plane, rowb},
+                                        {base + 30 * plane, pstep}};
+    const Log whole = calls(mixed);
+    REQUIRE(ok && whole == (Log{{'L', 0, 2, base, 0}, {'P', 2, 1, base + 8 * plane, pstep}, {'L', 3, 2, base + 20 * plane, 0}, {'P', 5, 1, base + 30 * plane, pstep}}));
+    for (size_t fail_at = 1; fail_at <= 4; ++fail_at) {
+        const Log cut = calls(mixed, fail_at);
+        REQUIRE(!ok && cut == Log(whole.begin(), whole.begin() + fail_at));
+    }
+    REQUIRE(calls(dense5, 1).size() == 1 && !ok);   // (the run that is still open when the planes end)
+    return 0;
+}
+
+// ---- cvs_overlap.h: the chunk schedule of a shard and the blocks of the ranks ----
+static int check_chunks_and_shards()
+{
+    using namespace cvs;
+    // computed from the expression host_rank held before chunk_starts existed
+    const struct { int n; std::vector<int> starts; } pinned[] = {
+        {1, {0, 1}}, {2, {0, 1, 2}}, {3, {0, 1, 3}}, {4, {0, 1, 4}}, {5, {0, 1, 3, 5}}, {8, {0, 1, 3, 8}}, {16, {0, 1, 3, 7, 16}},
+        {31, {0, 1, 3, 7, 15, 31}}, {32, {0, 1, 3, 7, 15, 32}}, {33, {0, 1, 3, 7, 15, 33}}, {64, {0, 2, 6, 14, 30, 64}},
+        {100, {0, 3, 9, 21, 45, 100}}, {1000, {0, 31, 93, 217, 465, 1000}}};
+    for (const auto& p : pinned) REQUIRE(chunk_starts(p.n, false) == p.starts);
+    for (int n = 1; n <= 4096; ++n) {
+        const std::vector<int> c = chunk_starts(n, false);
+        REQUIRE(c.size() >= 2 && c.size() <= 6 && c.front() == 0 && c.back() == n);
+        for (size_t k = 1; k < c.size(); ++k) REQUIRE(c[k] > c[k - 1]);
+        REQUIRE(chunk_starts(n, true) == (std::vector<int>{0, n}));
+    }
+    for (int n = 0; n <= 200; ++n)
+        for (int world = 1; world <= 17; ++world) {
+            int next = 0;
+            for (int rank = 0; rank < world; ++rank) {
+                int lo = -1, hi = -1;
+                shard_range(n, world, rank, &lo, &hi);
+                REQUIRE(lo == next && hi >= lo);   // the blocks tile [0, n) in rank order
+                for (int f = lo; f < hi; ++f) REQUIRE(f * world / n == rank);
+                next = hi;
+            }
+            REQUIRE(next == n);
+        }
+    return 0;
+}
+
+// ---- cvs_overlap.h: the gate between the thread that queues and the worker ----
+// Every wait below is bounded: a wake-up that gets lost fails the check (the worker is then released by stop() and joined) instead of
+// hanging it; only a stop() that releases nobody cannot be joined, and ends the program.
+static bool reaches(const std::atomic<int>& v, int want)
+{
+    const auto until = std::chrono::steady_clock::now() + std::chrono::seconds(20);
+    while (v.load() < want && std::chrono::steady_clock::now() < until) std::this_thread::sleep_for(std::chrono::microseconds(200));
+    return v.load() >= want;
+}
+
+static int check_gate()
+{
+    using namespace cvs;
+    for (int round = 0; round < 20; ++round) {
+        // the worker takes items 0 ... kItems - 1 as they are published, one or several at a time, and sees each exactly once, in order
+        const int kItems = 200;
+        Gate gate;
+        std::atomic<int> taken(0);
+        std::vector<int> seen;
+        bool stopped_early = false;
+        std::thread worker([&] {
+            for (int k = 0; k < kItems; ++k) {
+                if (!gate.wait(k)) { stopped_early = true; return; }
+                seen.push_back(k);
+                taken.store(k + 1);
+            }
+        });
+        for (int k = 0; k < kItems;) {
+            k = std::min(kItems, k + 1 + (int)(rnd() % 3));
+            gate.publish(k);
+            if (rnd() % 4 == 0) REQUIRE(reaches(taken, k) || (gate.stop(), worker.join(), false));   // the worker blocks again behind item k - 1
+        }
+        const bool all = reaches(taken, kItems);
+        gate.stop();   // after everything was published: nothing for a worker that has finished
+        worker.join();
+        REQUIRE(all && !stopped_early && (int)seen.size() == kItems);
+        for (int k = 0; k < kItems; ++k) REQUIRE(seen[k] == k);
+        REQUIRE(!gate.wait(0));   // stopped stays stopped
+    }
+    // stop() releases a worker that waits for an item that never comes, and wait() says so
+    for (int published : {0, 3}) {
+        Gate gate;
+        std::atomic<int> stage(0);
+        bool got = true;
+        gate.publish(published);
+        std::thread worker([&] {
+            bool before = true;
+            for (int k = 0; k < published; ++k) before = before && gate.wait(k);
+            stage.store(before ? 1 : -100);
+            got = gate.wait(published);
+            stage.store(2);
+        });
+        REQUIRE(reaches(stage, 1) || (gate.stop(), worker.join(), false));
+        std::this_thread::sleep_for(std::chrono::milliseconds(2));   // (the worker is most likely inside wait() now; either way it must come back)
+        REQUIRE(stage.load() == 1);
+        gate.stop();
+        if (!reaches(stage, 2)) {
+            std::fprintf(stderr, "host_logic_san: Gate::stop() did not release the waiting worker\n");
+            std::_Exit(1);
+        }
+        worker.join();
+        REQUIRE(!got);
+    }
+    return 0;
+}
 
 int main()
 {
@@ -277,6 +514,8 @@ int main()
         static_assert(kMaxResourceBytes == 0x7ffffff0u, "the host's limit is kMaxPlaneBytes of cvs_kernels_basis.hip");
     }
 
+    if (check_walk_runs() || check_chunks_and_shards() || check_gate()) return 1;
+
     // ---- taps ----
     float t[kMaxTaps];
     REQUIRE(host_make_taps(CVS_KIND_G2, 0, 4, 0.67f, t) == 0 && t[4] < 0.f && t[0] == t[8]);
@@ -284,6 +523,6 @@ int main()
     REQUIRE(host_make_taps(7, 0, 4, 0.67f, t) != 0 && host_make_taps(CVS_KIND_G2, 7, 4, 0.67f, t) != 0 && host_make_taps(CVS_KIND_G2, 0, kMaxWidth + 1, 0.67f, t) != 0);
     float w[kMaxBasis];
     for (float th : {0.f, 0.3f, -1.2f, 3.1415927f}) REQUIRE(host_steer_weights(CVS_KIND_G2, th, w) == 0 && host_steer_weights(CVS_KIND_G4, th, w) == 0);
-    std::printf("host_logic_san: argument checks, 20000 + 6000 overlap cases, CVS_OPTS fuzz, 480 state layouts, 14 plane layouts, taps: no sanitizer report\n");
+    std::printf("host_logic_san: argument checks, 20000 + 6000 overlap cases, CVS_OPTS fuzz, 480 state layouts, 14 plane layouts, 6000 copy walks, chunk schedule, shards, gate, taps: no sanitizer report\n");
     return 0;
 }

@@ -270,6 +270,63 @@ def test_byte_output_planes_padded_and_mixed_rejected(cv, world):
     nb.close()
 
 
+@pytest.mark.parametrize("persist", [False, True])
+@pytest.mark.parametrize("world", [1, 3])
+def test_host_planes_runs_that_break_and_continue(cv, world, persist):
+    """cvs_batch_run through the C ABI with host planes that make the copy coalescer work: input frames in slots 0 1 | 3 4 5 | 8 9 10 11 12
+    of one [15] block (dense runs of 2, 3 and 5) and an eleventh frame with padded rows in an array of its own; the three output maps in
+    slots 0 1 | 3 of an [n][4] block, so that a run breaks after two planes inside a frame and continues from slot 3 into slot 0 of the next
+    frame, one plane of a middle frame redirected to a padded array.  With three ranks the shards are 4 | 4 | 3 frames, and without kept
+    state a shard of 4 runs as chunks 1 | 3: runs are cut at chunk boundaries too.  f32 in / f32 out and 8-bit in / 8-bit out (normalised,
+    and gain 3.0): bit-identical to the same frames as one dense block, every byte around the planes untouched."""
+    import ctypes as C
+    from cvsteer_amd import _lib as L
+    from cvsteer_amd import batch
+    lib = L.lib()
+    n, rows, cols, sel = 11, 33, 70, (5, 6, 7)
+    in_slots, out_slots, moved = (0, 1, 3, 4, 5, 8, 9, 10, 11, 12), (0, 1, 3), (5, 1)
+    rng = np.random.default_rng(23)
+    nb = batch.NativeBatch.local((0,) * world)
+    nb.set_persist(persist)
+    cfg = L.BatchCfg(rows, cols, n, sum(1 << k for k in sel), 0, 1, 0)
+    for dtype, gains in ((np.float32, (None,)), (np.uint8, (0.0, 3.0))):
+        u8 = dtype == np.uint8
+        esz, mem = (1, L.MEM_HOST | L.DEPTH_U8) if u8 else (4, L.MEM_HOST)
+        dense = rng.integers(0, 256, (n, rows, cols), dtype=np.uint8) if u8 else rng.random((n, rows, cols), dtype=np.float32)
+        in_mark, out_mark = (0xEE, 0x5A) if u8 else (np.nan, np.nan)
+        block = np.full((15, rows, cols), in_mark, dtype)
+        block[list(in_slots)] = dense[:10]
+        own = np.full((rows, cols + 9), in_mark, dtype)
+        own[:, :cols] = dense[10]
+        block_before, own_before = block.tobytes(), own.tobytes()
+        ins = (L.Plane * n)(*([L.Plane(block[k].ctypes.data, rows, cols, cols * esz, mem) for k in in_slots] +
+                             [L.Plane(own.ctypes.data, rows, cols, (cols + 9) * esz, mem)]))
+        for gain in gains:
+            want = nb.run_to_u8(dense, outputs=sel, gain=gain)[0] if u8 else nb.run(dense, n, (rows, cols), outputs=sel)[0]
+            oblock = np.full((n, 4, rows, cols), out_mark, dtype)
+            opad = np.full((rows, cols + 11), out_mark, dtype)
+            outs = (L.Plane * (8 * n))()
+            for i in range(n):
+                for j, k in enumerate(sel):
+                    outs[i * 8 + k] = L.Plane(oblock[i, out_slots[j]].ctypes.data, rows, cols, cols * esz, mem)
+            outs[moved[0] * 8 + sel[moved[1]]] = L.Plane(opad.ctypes.data, rows, cols, (cols + 11) * esz, mem)
+            if u8:
+                assert lib.cvs_batch_set_u8_gain(nb._b, C.c_float(gain)) == 0
+            t = L.BatchTiming()
+            assert lib.cvs_batch_run(nb._b, C.byref(cfg), ins, outs, C.byref(t)) == 0, lib.cvs_batch_last_error(nb._b)
+            untouched = (lambda a: bool(np.isnan(a).all())) if not u8 else (lambda a: bool((a == out_mark).all()))
+            for i in range(n):
+                for j in range(3):
+                    if (i, j) == moved:
+                        assert np.array_equal(opad[:, :cols], want[i, j]) and untouched(opad[:, cols:]) and untouched(oblock[i, out_slots[j]])
+                    else:
+                        assert np.array_equal(oblock[i, out_slots[j]], want[i, j]), (i, j)
+            assert untouched(oblock[:, 2])
+            assert block.tobytes() == block_before and own.tobytes() == own_before
+            assert t.scatter_ms > 0 and t.gather_ms > 0 and t.compute_ms >= t.gather_ms
+    nb.close()
+
+
 _AGREE_SCRIPT = r"""
 import ctypes as C, sys, torch
 import cvsteer_amd as cv
