@@ -54,6 +54,13 @@ class Chain(C.Structure):
 
 CHAIN_CLOSED, CHAIN_HEAD_JUNCTION, CHAIN_TAIL_JUNCTION = 1, 2, 4
 
+
+class ChainMeasure(C.Structure):
+    """struct cvs_chain_measure"""
+    _fields_ = [("axial", C.c_int32), ("diagonal", C.c_int32), ("other", C.c_int32), ("peak_index", C.c_int32),
+                ("peak", C.c_float), ("weakest", C.c_float), ("sum", C.c_double), ("length", C.c_double)]
+
+
 _PP = C.POINTER(Plane)
 _FP = C.POINTER(C.c_float)
 _IP = C.POINTER(C.c_int)
@@ -100,6 +107,8 @@ SIGNATURES = {
     "cvs_contour_chains": (C.c_int, [C.c_void_p, _PP, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, _IP, _IP]),
     "cvs_chain_polylines": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p,
                                       C.c_void_p, C.c_int, _IP]),
+    "cvs_chain_refine": (C.c_int, [C.c_void_p, _PP, _PP, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+    "cvs_chain_measures": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "cvs_link": (C.c_int, [C.c_void_p, C.c_int, _PP, C.c_float, C.c_float, C.c_int, C.c_float, _PP, C.c_void_p]),
     "cvs_nonmax_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _PP, _PP, _PP]),
     "cvs_contours_batch": (C.c_int, [C.c_void_p, _PP, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float, _PP]),

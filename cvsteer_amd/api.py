@@ -712,6 +712,111 @@ class _CallerPipeline:
         points, chains = self.contour_chains(mask)
         return self.chain_polylines(points, chains, eps, return_index=return_index)
 
+    # -- contour edgels (extension beyond the reference): cvs_chain_refine / cvs_chain_measures --
+    MEASURE_DTYPE = np.dtype([("axial", "<i4"), ("diagonal", "<i4"), ("other", "<i4"), ("peak_index", "<i4"), ("peak", "<f4"),
+                              ("weakest", "<f4"), ("sum", "<f8"), ("length", "<f8")])
+
+    @staticmethod
+    def _chain_array(a, dev, dtype_np, width, what):
+        """`a` as a contiguous array of `dtype_np` with `width` columns (0: one-dimensional): a CUDA tensor when dev, else numpy"""
+        if a is None:
+            return None
+        if dev:
+            if not (_is_torch(a) and a.is_cuda):
+                raise ValueError("%s: on the device like points" % what)
+            a = a.to(getattr(torch, np.dtype(dtype_np).name)).contiguous()
+        else:
+            if _is_torch(a) and a.is_cuda:
+                raise ValueError("%s: on the host like points" % what)
+            a = np.ascontiguousarray(a.numpy() if _is_torch(a) else a, dtype_np)
+        if (a.ndim != 2 or a.shape[1] != width) if width else a.ndim != 1:
+            raise ValueError("%s must be %s" % (what, "(N, %d)" % width if width else "(N,)"))
+        return a
+
+    @staticmethod
+    def _is_out(a, dev, dtype_np, shape):
+        """is `a` a contiguous array of that type and shape where the call writes: a CUDA tensor when dev, else a numpy array"""
+        if dev:
+            return _is_torch(a) and a.is_cuda and a.dtype == getattr(torch, np.dtype(dtype_np).name) and tuple(a.shape) == shape and a.is_contiguous()
+        return isinstance(a, np.ndarray) and a.dtype == dtype_np and a.shape == shape and a.flags.c_contiguous
+
+    @staticmethod
+    def _array_ptr(a):
+        if a is None or (a.numel() if _is_torch(a) else a.size) == 0:
+            return None
+        return C.c_void_p(a.data_ptr() if _is_torch(a) else a.ctypes.data)
+
+    def chain_refine(self, points, map, theta=None, out=None):
+        """Sub-pixel position and strength of every chain point (cvs_chain_refine).  points: (N, 2) int32 of (x, y) as contour_chains
+        returns them; map: the UN-THINNED response the contours were found in (the edges / dark / bright output of pipeline, not the
+        output of nonmax); theta=None: the object's dominant orientation (of the frame select_frame chose).  Returns (xy (N, 2) float32
+        of (xs, ys), strength (N,) float32).  Torch CUDA points take the device path -- one launch, nothing read back, capturable -- and
+        give tensors on their device; numpy points take the host path (torch CPU tensors too, and come back as such).  out: an
+        (xy, strength) pair to write into instead.  include/cvsteer_hip.h has the contract."""
+        if theta is None:
+            self._caller_check("cvs_chain_refine")   # (the object's own orientation: G4 has one with extensions only)
+        dev = _is_torch(points) and points.is_cuda
+        back = _is_torch(points) and not dev
+        points = self._chain_array(points, dev, np.int32, 2, "points")
+        n = int(points.shape[0])
+        if out is not None:
+            xy, strength = out
+            if not (self._is_out(xy, dev, np.float32, (n, 2)) and self._is_out(strength, dev, np.float32, (n,))):
+                raise ValueError("out: contiguous float32 (N, 2) and (N,) arrays, where points are")
+        elif dev:
+            xy = torch.empty((n, 2), dtype=torch.float32, device=points.device)
+            strength = torch.empty((n,), dtype=torch.float32, device=points.device)
+        else:
+            xy, strength = np.empty((n, 2), np.float32), np.empty((n,), np.float32)
+        self._bind_stream(points, map, *([] if theta is None else [theta]))
+        pm = _plane(map)
+        pt = None if theta is None else C.byref(_plane(theta))
+        self._check(lib().cvs_chain_refine(self._h, C.byref(pm), pt, self._array_ptr(points), n, self._array_ptr(xy), self._array_ptr(strength),
+                                           L.MEM_DEVICE if dev else L.MEM_HOST), "cvs_chain_refine")
+        if back and out is None:
+            xy, strength = torch.from_numpy(xy), torch.from_numpy(strength)
+        return xy, strength
+
+    def chain_measures(self, points, chains, strength=None, xy=None, out=None):
+        """One record per chain (cvs_chain_measures): a numpy structured array with the fields of `cvs_chain_measure` (axial, diagonal,
+        other: steps by kind; peak_index, peak, weakest, sum of `strength`; length: the Euclidean length, of the sub-pixel `xy` when
+        given, else of the integer points).  points (N, 2) int32 and chains (M, 4) int32 as contour_chains returns them, strength (N,)
+        and xy (N, 2) float32 as chain_refine returns them.  Torch CUDA arrays take the device path: the table is written on the device
+        and downloaded for the return value -- or, with out= an (M, 40) uint8 CUDA tensor, left there (nothing read back, capturable;
+        out.cpu().numpy().view(MEASURE_DTYPE) reads it) and `out` is returned."""
+        dev = _is_torch(points) and points.is_cuda
+        points = self._chain_array(points, dev, np.int32, 2, "points")
+        chains = self._chain_array(chains, dev, np.int32, 4, "chains")
+        strength = self._chain_array(strength, dev, np.float32, 0, "strength")
+        xy = self._chain_array(xy, dev, np.float32, 2, "xy")
+        n, m = int(points.shape[0]), int(chains.shape[0])
+        if (strength is not None and strength.shape[0] != n) or (xy is not None and xy.shape[0] != n):
+            raise ValueError("strength and xy: one entry per point")
+        size = self.MEASURE_DTYPE.itemsize
+        if out is not None:
+            if not (dev and self._is_out(out, dev, np.uint8, (m, size))):
+                raise ValueError("out: a contiguous (M, %d) uint8 CUDA tensor, with device arrays" % size)
+            table = out
+        elif dev:
+            table = torch.empty((m, size), dtype=torch.uint8, device=points.device)
+        else:
+            table = np.zeros(m, self.MEASURE_DTYPE)
+        if dev:
+            self._bind_stream(points)
+        self._check(lib().cvs_chain_measures(self._h, self._array_ptr(points), n, self._array_ptr(chains), m, self._array_ptr(xy),
+                                             self._array_ptr(strength), self._array_ptr(table), L.MEM_DEVICE if dev else L.MEM_HOST),
+                    "cvs_chain_measures")
+        if out is not None or not dev:
+            return table
+        return table.cpu().numpy().view(self.MEASURE_DTYPE).reshape(m)
+
+    def contour_edgels(self, mask, map, theta=None):
+        """contour_chains(mask), chain_refine on the un-thinned `map` the mask came from, chain_measures on both: the linked contours of
+        a mask as sub-pixel edgels.  Returns (points, chains, xy, strength, measures)."""
+        points, chains = self.contour_chains(mask)
+        xy, strength = self.chain_refine(points, map, theta)
+        return points, chains, xy, strength, self.chain_measures(points, chains, strength=strength, xy=xy)
+
     def contours(self, image, low, high, min_area=0, min_peak=0.0):
         """Thin, linked contours of one image: pipeline(image) -> nonmax(edges, dark, bright) on the object's own theta ->
         hysteresis(low, high).  Returns three uint8 masks (edges, dark lines, bright lines).  min_area > 0 or min_peak > 0: the

@@ -7,6 +7,7 @@
 #include <cvsteer/SteerableFiltersG2.h>
 #include <cvsteer/SteerableFiltersG4.h>
 
+#include <cstddef>
 #include <mutex>
 #include <stdexcept>
 #include <string>
@@ -140,6 +141,43 @@ int approx_contours(cvs_handle h, const std::vector<std::vector<Point> >& chains
         for (int k = 0; k < t.length; ++k) out[c].push_back(Point(vtx[2 * (size_t)(t.start + k)], vtx[2 * (size_t)(t.start + k) + 1]));
     }
     *n = nv;
+    return CVS_OK;
+}
+
+// the chains packed into one point list, one call on the handle's own theta, the pairs unpacked again: no arithmetic on the host
+int refine_contours(cvs_handle h, const Mat1f& response, const std::vector<std::vector<Point> >& chains, std::vector<std::vector<float> >& xs,
+                    std::vector<std::vector<float> >& ys, std::vector<std::vector<float> >* strength, int* n)
+{
+    size_t np = 0;
+    for (size_t c = 0; c < chains.size(); ++c) np += chains[c].size();
+    if (np > (size_t)1 << 30) return CVS_E_SIZE;
+    std::vector<int32_t> pts(np * 2);
+    std::vector<float> xy(np * 2), str(strength ? np : 0);
+    size_t at = 0;
+    for (size_t c = 0; c < chains.size(); ++c)
+        for (size_t k = 0; k < chains[c].size(); ++k, ++at) {
+            pts[2 * at] = chains[c][k].x;
+            pts[2 * at + 1] = chains[c][k].y;
+        }
+    cvs_plane pr = view(response);
+    const int rc = cvs_chain_refine(h, &pr, 0, pts.data(), (int)np, xy.data(), strength ? str.data() : 0, CVS_MEM_HOST);
+    if (rc != CVS_OK) return rc;
+    xs.assign(chains.size(), std::vector<float>());
+    ys.assign(chains.size(), std::vector<float>());
+    if (strength) strength->assign(chains.size(), std::vector<float>());
+    at = 0;
+    for (size_t c = 0; c < chains.size(); ++c) {
+        const size_t len = chains[c].size();
+        xs[c].resize(len);
+        ys[c].resize(len);
+        for (size_t k = 0; k < len; ++k) {
+            xs[c][k] = xy[2 * (at + k)];
+            ys[c][k] = xy[2 * (at + k) + 1];
+        }
+        if (strength) (*strength)[c].assign(str.begin() + (std::ptrdiff_t)at, str.begin() + (std::ptrdiff_t)(at + len));
+        at += len;
+    }
+    *n = (int)np;
     return CVS_OK;
 }
 
@@ -402,6 +440,14 @@ int SteerableFiltersG2::approxContours(const std::vector<std::vector<Point> >& c
     return n;
 }
 
+int SteerableFiltersG2::refineContours(const Mat1f& response, const std::vector<std::vector<Point> >& chains, std::vector<std::vector<float> >& xs,
+                                       std::vector<std::vector<float> >& ys, std::vector<std::vector<float> >* strength)
+{
+    int n = 0;
+    check(refine_contours(m_handle, response, chains, xs, ys, strength, &n), "cvs_chain_refine");
+    return n;
+}
+
 void SteerableFiltersG2::phaseWeights(const Mat1f& phase, Mat1f& lambda, float phi, bool signum, float k)
 {
     std::lock_guard<std::mutex> lock(g_static_mutex);
@@ -504,6 +550,14 @@ int SteerableFiltersG4::approxContours(const std::vector<std::vector<Point> >& c
 {
     int n = 0;
     check(approx_contours(m_handle, chains, flags, epsilon, polylines, &n), "cvs_chain_polylines");
+    return n;
+}
+
+int SteerableFiltersG4::refineContours(const Mat1f& response, const std::vector<std::vector<Point> >& chains, std::vector<std::vector<float> >& xs,
+                                       std::vector<std::vector<float> >& ys, std::vector<std::vector<float> >* strength)
+{
+    int n = 0;
+    check(refine_contours(m_handle, response, chains, xs, ys, strength, &n), "cvs_chain_refine");
     return n;
 }
 

@@ -74,6 +74,12 @@ public:
     // treated as a cycle), 0 = all chains open.  polylines[c] = the kept points of chains[c] in order.  Returns the number of vertices
     int approxContours(const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags, float epsilon,
                        std::vector<std::vector<Point> >& polylines);
+    // contour edgels (extension, cvs_chain_refine): the sub-pixel position (xs[c][k], ys[c][k]) of point k of chains[c], and optionally its
+    // strength there, from `response` -- the UN-THINNED map the contours were found in (what nonMaxSuppression was given, not what it
+    // returned) -- across the dominant orientation m_theta, by the contract of include/cvsteer_hip.h.  A point outside the image throws.
+    // Returns the number of points
+    int refineContours(const Mat1f& response, const std::vector<std::vector<Point> >& chains, std::vector<std::vector<float> >& xs,
+                       std::vector<std::vector<float> >& ys, std::vector<std::vector<float> >* strength = 0);
 
 protected:
     // the reference's protected members, same names (SteerableFiltersG2.h:62-66).  m_g1..m_h4 are the 7 tap vectors; the

@@ -40,6 +40,10 @@ public:
     // addition: polylines of the chains, as in SteerableFiltersG2 (cvs_chain_polylines)
     int approxContours(const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags, float epsilon,
                        std::vector<std::vector<Point> >& polylines);
+    // addition: sub-pixel chain points, as in SteerableFiltersG2 (cvs_chain_refine on the object's own theta: it throws where the object has
+    // no orientation state)
+    int refineContours(const Mat1f& response, const std::vector<std::vector<Point> >& chains, std::vector<std::vector<float> >& xs,
+                       std::vector<std::vector<float> >& ys, std::vector<std::vector<float> >* strength = 0);
 
 protected:
     // the reference's protected members, same names (SteerableFiltersG4.h:50-56): 11 tap vectors; the planes m_g4a..m_h4f

@@ -414,6 +414,68 @@ int cvs_chain_polylines(cvs_handle h,
                         int mem,                                    /* CVS_MEM_HOST / CVS_MEM_DEVICE: all five arrays */
                         int* n_vertices);                           /* required, always set */
 
+/* ---- EXTENSION beyond the reference: contour edgels -- the sub-pixel position of every chain point, and measures per chain ----
+ * Neither call reads anything back: with device arrays (and device planes) each queues its launches on the handle's stream and returns, and
+ * both may be captured.  With host arrays the arrays are staged in handle scratch (grown only, freed by cvs_destroy), the call synchronises
+ * the stream, and it returns CVS_E_UNSUPPORTED while the stream is being captured.  Nothing is written when an argument is rejected.
+ * Sub-pixel polyline vertices need no call of their own: they are xy[index[k]], with the index cvs_chain_polylines returns. */
+
+/* EXTENSION: refine the points (x, y) of a point list -- as cvs_contour_chains writes them -- to the sub-pixel position of the contour and
+ * its strength there.  map: an f32 plane of the handle's image size, host or device, pitched or dense.  It is the UN-THINNED response the
+ * points were found in (e.g. the edges / dark / bright output of cvs_pipeline, the input of cvs_nonmax): in a thinned map the neighbours of
+ * a kept pixel are 0 and the refinement means nothing.  theta: as in cvs_nonmax; NULL = the handle's own CVS_PLANE_THETA of the frame
+ * chosen by cvs_select_frame (CVS_E_STATE without orientation state).
+ * Contract, per point: m = map[y][x]; (c, s), ax, ay, sx, sy, the major axis, w and the forward / backward samples vf / vb are those of
+ * the cvs_nonmax contract -- same operations, same rounding, neighbours outside the image read as 0.0f.  a = m - vb, b = m - vf.  If
+ * a > 0 && b >= 0 (the keep test of cvs_nonmax; false for NaN) then t = 0.5f * ((a - b) / (a + b)), every operation rounded on its own,
+ * the division correctly rounded -- rounding is monotone, so |t| <= 0.5 without a clamp.  Position: if ax >= ay,
+ * xs = (float)x + sx * t and ys = (float)y + sy * (t * w); otherwise xs = (float)x + sx * (t * w) and ys = (float)y + sy * t (sx, sy are
+ * +-1: the sign flips are exact).  strength = m + 0.25f * ((a - b) * t): the vertex of the parabola through (vb, m, vf).  Where the test
+ * fails -- NaN in m, theta or a sample included -- t = 0, the position is the pixel centre ((float)x, (float)y) and strength is m bit for
+ * bit (no product with a NaN sample or weight is formed).
+ * xy receives n_points (xs, ys) pairs, strength (may be NULL) n_points floats; points, xy and strength are all in host or all in device
+ * memory (mem).  Coordinates are addresses here: the kernel compares them with cols / rows before any load, and a point outside the image
+ * stores NaN in xs, ys and strength without the map being read for it; a HOST points array with such a point is refused with
+ * CVS_E_BADARG before anything is queued.
+ * n_points == 0: CVS_OK, nothing queued.  CVS_E_BADARG: a negative n_points, points or xy NULL with n_points > 0, a pointer not aligned to
+ * 4 bytes, an invalid mem, xy or strength overlapping points, map, theta or each other; CVS_E_SIZE: a plane of another size than the
+ * handle's image, n_points > 2^30; CVS_E_STATE: no image size yet.  One kernel launch, one lane per point. */
+int cvs_chain_refine(cvs_handle h, const cvs_plane* map, const cvs_plane* theta,
+                     const int32_t* points, int n_points,   /* (x, y) pairs */
+                     float* xy,                              /* n_points (xs, ys) pairs */
+                     float* strength,                        /* NULL, or n_points floats */
+                     int mem);                               /* CVS_MEM_HOST / CVS_MEM_DEVICE: the three arrays */
+
+/* EXTENSION: table[c] measures chain c of a chain table.  Needs no image size (any handle, before or after a setup).
+ * STEPS.  Step i of a chain of L points goes from point i to point i + 1, i < L - 1; a chain with CVS_CHAIN_CLOSED has one more, from
+ * its last point to its first.  With (dx, dy) the integer step: |dx| + |dy| == 1 is axial, |dx| == |dy| == 1 diagonal, anything else
+ * `other` (always 0 for a table of cvs_contour_chains).  length = the sum over the steps of sqrt(dx * dx + dy * dy) in double, each
+ * operation rounded on its own, with dx, dy the differences of the (xs, ys) pairs of `xy` widened to double when xy != NULL, of the
+ * integer points otherwise.
+ * STRENGTHS.  peak / weakest: the largest / smallest strength of the chain that is not NaN (-INFINITY / +INFINITY if there is none);
+ * peak_index: the position in `points` of the first point whose strength equals peak (-1 if none); sum: the IEEE double sum of the
+ * chain's strengths (a NaN propagates).  strength == NULL: peak_index -1, peak -INFINITY, weakest +INFINITY, sum 0.
+ * The order of the additions of sum and length is fixed by the chain's own length and flags (a lane adds every 64th or 256th term in
+ * ascending order, the lanes are combined by a butterfly): the same call twice gives the same bits.  No floating-point atomic is used.
+ * points, chains, xy, strength and table are all in host or all in device memory (mem).  A HOST table with an entry that violates
+ * start >= 0, length >= 1, start + length <= n_points: CVS_E_BADARG.  On the device such an entry yields an all-zero record with
+ * peak_index -1, and no load leaves the arrays; coordinates are never used as addresses.  CVS_E_BADARG as well: a negative count, a
+ * required array missing, an invalid mem, a pointer not aligned to 4 bytes, a table that overlaps an input; n_points > 2^30: CVS_E_SIZE.
+ * n_chains == 0: CVS_OK, nothing queued.  Two launches for any table -- one wave per chain of up to 256 points, one 256-lane workgroup per
+ * longer chain -- so the launch sequence depends on (n_points, n_chains) alone. */
+typedef struct cvs_chain_measure {   /* 40 bytes */
+    int32_t axial, diagonal, other;  /* steps between consecutive points, by kind */
+    int32_t peak_index;              /* position in `points` of the first point that attains `peak`; -1 if none */
+    float   peak, weakest;           /* largest / smallest non-NaN strength; -INFINITY / +INFINITY if none */
+    double  sum;                     /* IEEE sum of the chain's strengths (NaN propagates) */
+    double  length;                  /* sum of the Euclidean step lengths, in double */
+} cvs_chain_measure;
+int cvs_chain_measures(cvs_handle h, const int32_t* points, int n_points,
+                       const cvs_chain* chains, int n_chains,
+                       const float* xy,        /* NULL: lengths from the integer points; else from the sub-pixel pairs */
+                       const float* strength,  /* NULL: peak_index -1, peak -INF, weakest +INF, sum 0 */
+                       cvs_chain_measure* table, int mem);
+
 /* ---- EXTENSION beyond the reference: the contour chain on the batch axis -- cvs_link, cvs_nonmax_batch, cvs_contours_batch ----
  * None of the three reads anything back: with device planes they queue a launch sequence that depends on the image size, the number of
  * planes and how the planes lie in memory (one constant stride, or not) -- never on what the planes hold -- and return. */
