@@ -22,8 +22,13 @@
  *     (oracle/ref_taps.mk -> tests/golden/taps_ref.json).
  *   - full G2 pipeline: the reference's own golden JPEGs (test/test.cpp:70-108) at the
  *     reference's own tolerance (mean-L1 <= 1.0 of 255); we score ~0.01-0.03.
- *   - per-plane float values at the 1e-5 level: NOT pinned by any reference data
- *     ("parity unpinned" at that level) -- checked against an f64-accumulated restatement only.
+ *   - per-plane float values: pinned by a run of the reference's own source files, compiled where they lie over the stand-in
+ *     headers of oracle/cvshim (oracle/ref_run.mk -> tests/golden/ref_run/, tests/test_reference_run_cpu.py): every function below
+ *     is held to those planes stage by stage at 1e-6 of the stage's largest term, most of them bit for bit.  This pins what the
+ *     reference's author wrote: tables, pairings, signs, polynomials, gates, call order.
+ *   - still RECALLED, because the stand-in takes them from here: the OpenCV primitives themselves -- sepFilter2D's row / column
+ *     arithmetic and border, cartToPolar's arctangent polynomial, polarToCart, eager one-plane-per-operator matrix arithmetic
+ *     (MatExpr's folded forms differ by an ulp), double scalars narrowed to float in arithmetic and in Mat > scalar.
  *
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may call into this.
  * The product path (cvsteer_amd/, include/) never links or imports it.

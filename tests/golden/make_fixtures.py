@@ -10,6 +10,9 @@ Run in the build container only (needs /root/reference):  python tests/golden/ma
   Pillow (stand-in for cv::imdecode(IMREAD_GRAYSCALE), test.cpp:53-56), so GPU-box tests
   do not depend on a JPEG decoder.
 * taps_ref.json is produced separately by `make -C oracle -f ref_taps.mk golden`.
+* ref_run/ -- `python tests/golden/make_fixtures.py ref_run <binary>` (what `make -C oracle -f ref_run.mk golden` runs): the six
+  numpy input planes of tests/ref_run_fixture.py and every plane the reference's own source files write for them through
+  tests/cpp/ref_sequence.cpp, packed into float32 .npy stacks with an index.json.  Data, not code.
 """
 import io, os, re, sys
 import numpy as np
@@ -41,5 +44,18 @@ def main():
         np.save(os.path.join(HERE, name + "_u8.npy"), img)
         print(name, len(raw), "bytes ->", img.shape, img.dtype)
 
+def ref_run(exe):
+    import tempfile
+    sys.path.insert(0, os.path.dirname(HERE))
+    import ref_run_fixture as rr
+    inputs = rr.make_inputs()
+    with tempfile.TemporaryDirectory() as tin, tempfile.TemporaryDirectory() as tout:
+        planes, points = rr.run_driver(exe, inputs, tin, tout)
+    planes.update(inputs)
+    rr.pack(planes, points, os.path.join(HERE, "ref_run"))
+    print("ref_run:", len(planes), "planes ->", os.path.join(HERE, "ref_run"))
+
 if __name__ == "__main__":
+    if len(sys.argv) == 3 and sys.argv[1] == "ref_run":
+        sys.exit(ref_run(sys.argv[2]))
     sys.exit(main())

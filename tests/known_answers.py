@@ -31,3 +31,24 @@ def impulse_planes(golden_dir, kind, rows, cols, r, c):
             for x in range(max(0, c - w), min(cols, c + w + 1)):
                 out[p, y, x] = np.float32(ky[r - y + w]) * np.float32(kx[c - x + w])
     return out
+
+
+def basis_planes(golden_dir, kind, image):
+    """the basis planes of any image by the same rule, in float32: the reference's tap tables at the default (width, spacing), its kernel
+    pairs, the borders reflected without repeating the edge pixel (BORDER_REFLECT_101 = numpy's 'reflect').  Row pass first, every
+    product and sum a float32; the order of the column sum is not sepFilter2D's, so this agrees with it to rounding only"""
+    taps = reference_taps(golden_dir, kind)
+    w = DEFAULTS[kind][0]
+    img = np.pad(np.asarray(image, np.float32), w, mode="reflect")
+    rows, cols = image.shape
+    out = np.empty((len(PAIRS[kind]), rows, cols), np.float32)
+    for p, (kxn, kyn) in enumerate(PAIRS[kind]):
+        kx, ky = taps[kxn], taps[kyn]
+        r = np.zeros((rows + 2 * w, cols), np.float32)
+        for i in range(2 * w + 1):
+            r += kx[i] * img[:, i:i + cols]
+        acc = np.zeros((rows, cols), np.float32)
+        for j in range(2 * w + 1):
+            acc += ky[j] * r[j:j + rows]
+        out[p] = acc
+    return out

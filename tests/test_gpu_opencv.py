@@ -3,7 +3,12 @@ box").  No image this build has run on has had cv2 -- the modu
 does, this is the literal reference call sequence (cvsteer/SteerableFiltersG2.cpp:62-99, 107-112, 137-177;
 SteerableFiltersG4.cpp:69-80, 114-122) next to the HIP planes AND next to the oracle, so that every `[recalled]` item of
 SURVEY.md 8(c) (fastAtan32f constants, SymmColumnFilter order, scalar narrowing) is finally checked against the real thing.
-Nothing of OpenCV is vendored; nothing here runs in the product path."""
+Nothing of OpenCV is vendored; nothing here runs in the product path.
+
+Since tests/golden/ref_run/ exists, what the reference's own source files wrote -- tables, pairings, signs, polynomials, gates, call
+order -- is pinned without OpenCV (tests/test_reference_run_cpu.py, tests/test_gpu_reference_run.py: the reference's .cpp files run over
+the stand-in headers of oracle/cvshim).  What only this module can pin is what that stand-in recalls: the arithmetic of sepFilter2D,
+cartToPolar and polarToCart themselves, MatExpr's folding of scalar expressions, and the narrowing of double scalars."""
 import numpy as np
 import pytest
 
