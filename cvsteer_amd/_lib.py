@@ -109,6 +109,9 @@ SIGNATURES = {
                                       C.c_void_p, C.c_int, _IP]),
     "cvs_chain_refine": (C.c_int, [C.c_void_p, _PP, _PP, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
     "cvs_chain_measures": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "cvs_contour_chains_batch": (C.c_int, [C.c_void_p, C.c_int, _PP, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, _IP, _IP]),
+    "cvs_chain_refine_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _PP, _PP, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_int]),
     "cvs_link": (C.c_int, [C.c_void_p, C.c_int, _PP, C.c_float, C.c_float, C.c_int, C.c_float, _PP, C.c_void_p]),
     "cvs_nonmax_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _PP, _PP, _PP]),
     "cvs_contours_batch": (C.c_int, [C.c_void_p, _PP, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float, _PP]),

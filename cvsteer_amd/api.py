@@ -964,6 +964,124 @@ class _CallerPipeline:
         self._batch_keepalive = (planes, out)
         return out
 
+    # -- contour chains and sub-pixel chain points on the batch axis (extension): cvs_contour_chains_batch / cvs_chain_refine_batch --
+    def _plane_block(self, a, what):
+        """the planes of `a` -- an [N, H, W] or [F, K, H, W] block (a CUDA tensor: descriptors filled in arithmetically), or a sequence of
+        planes or of sequences of planes -- as (cvs_plane array pointer, number of planes, what to keep alive, leading shape)"""
+        f32u8 = (torch.float32, torch.uint8) if torch is not None else ()
+        for nd in (3, 4):
+            if self._is_block(a, nd, f32u8):
+                lead = tuple(int(v) for v in a.shape[:nd - 2])
+                return self._block_planes(a, nd - 2).ctypes.data_as(L._PP), int(np.prod(lead)), [a], lead
+        flat, lead = [], None
+        for item in a:
+            if (_is_torch(item) or isinstance(item, np.ndarray)) and item.ndim == 2:
+                flat.append(item)
+            else:
+                row = list(item)
+                if lead is not None and lead[1] != len(row):
+                    raise ValueError("%s: the same number of planes in every frame" % what)
+                lead = (0, len(row))
+                flat.extend(row)
+        if not flat:
+            raise ValueError("%s: at least one plane" % what)
+        lead = (len(flat),) if lead is None else (len(flat) // lead[1], lead[1])
+        return _planes(flat), len(flat), flat, lead
+
+    def contour_chains_batch(self, masks):
+        """contour_chains for n masks in one launch sequence with one read-back (cvs_contour_chains_batch).  masks: an [N, H, W] or
+        [F, K, H, W] block (uint8 or float32), or a sequence of planes, all on the device or all on the host.  Returns (points, chains,
+        ranges): the concatenation over the planes z of contour_chains(masks[z]) -- points (P, 2) int32 of (x, y) inside their plane,
+        chains (M, 4) int32 of (start, length, flags, plane) with start counting through all planes -- and ranges (n + 1, 2) int32:
+        ranges[z] = (first chain, first point) of plane z, ranges[n] the totals.  The chains of plane z are chains[ranges[z, 0]:
+        ranges[z + 1, 0]].  Tensors on the masks' device for CUDA masks, numpy arrays for numpy masks (torch CPU masks come back as
+        torch CPU tensors).  chain_polylines and chain_measures take points and chains as they are; chain_refine_batch takes ranges."""
+        pm, n, keep, _ = self._plane_block(masks, "contour_chains_batch")
+        first = keep[0]
+        self._bind_stream(*keep)
+        dev = _is_torch(first) and first.is_cuda
+        np_, nc = C.c_int(0), C.c_int(0)
+        rc = lib().cvs_contour_chains_batch(self._h, n, pm, None, 0, None, 0, None, L.MEM_HOST, C.byref(np_), C.byref(nc))
+        if rc != L.E_SIZE:
+            self._check(rc, "cvs_contour_chains_batch")
+        if dev:
+            pts = torch.empty((np_.value, 2), dtype=torch.int32, device=first.device)
+            chains = torch.empty((nc.value, 4), dtype=torch.int32, device=first.device)
+            ranges = torch.empty((n + 1, 2), dtype=torch.int32, device=first.device)
+        else:
+            pts, chains, ranges = np.empty((np_.value, 2), np.int32), np.empty((nc.value, 4), np.int32), np.empty((n + 1, 2), np.int32)
+        self._check(lib().cvs_contour_chains_batch(self._h, n, pm, self._array_ptr(pts), np_.value, self._array_ptr(chains), nc.value,
+                                                   self._array_ptr(ranges), L.MEM_DEVICE if dev else L.MEM_HOST, C.byref(np_), C.byref(nc)),
+                    "cvs_contour_chains_batch")
+        if _is_torch(first) and not dev:
+            pts, chains, ranges = torch.from_numpy(pts), torch.from_numpy(chains), torch.from_numpy(ranges)
+        return pts, chains, ranges
+
+    def chain_refine_batch(self, points, ranges, maps, theta=None, out=None):
+        """chain_refine for the point list of contour_chains_batch in one launch (cvs_chain_refine_batch).  points, ranges: as
+        contour_chains_batch returns them for F * K planes; maps: the UN-THINNED responses the masks came from, an [F, K, H, W] block (K in
+        1..3) or a sequence of F sequences of K planes; theta: [F, H, W] (or F planes), None = the dominant orientation of frames 0 .. F-1
+        of the last pipeline_batch.  Returns (xy (P, 2) float32, strength (P,) float32), every value that of select_frame(z // K);
+        chain_refine(points of plane z, maps[z // K][z % K]).  CUDA points take the device path -- nothing read back, capturable --; numpy
+        points the host path (torch CPU tensors too, and come back as such).  out: an (xy, strength) pair to write into instead."""
+        if theta is None:
+            self._caller_check("cvs_chain_refine_batch")
+        dev = _is_torch(points) and points.is_cuda
+        back = _is_torch(points) and not dev
+        points = self._chain_array(points, dev, np.int32, 2, "points")
+        ranges = self._chain_array(ranges, dev, np.int32, 2, "ranges")
+        pm, n, keep, lead = self._plane_block(maps, "chain_refine_batch")
+        if len(lead) != 2 or not 1 <= lead[1] <= 3:
+            raise ValueError("chain_refine_batch: maps are F frames of K planes each, K in 1..3")
+        if int(ranges.shape[0]) != n + 1:
+            raise ValueError("ranges: one row per plane and one for the totals")
+        pt, ths = None, []
+        if theta is not None:
+            pt, nt, ths, _ = self._plane_block(theta, "theta")
+            if nt != lead[0]:
+                raise ValueError("theta: one plane per frame")
+        npts = int(points.shape[0])
+        if out is not None:
+            xy, strength = out
+            if not (self._is_out(xy, dev, np.float32, (npts, 2)) and self._is_out(strength, dev, np.float32, (npts,))):
+                raise ValueError("out: contiguous float32 (N, 2) and (N,) arrays, where points are")
+        elif dev:
+            xy = torch.empty((npts, 2), dtype=torch.float32, device=points.device)
+            strength = torch.empty((npts,), dtype=torch.float32, device=points.device)
+        else:
+            xy, strength = np.empty((npts, 2), np.float32), np.empty((npts,), np.float32)
+        self._bind_stream(points, *keep, *ths)
+        self._check(lib().cvs_chain_refine_batch(self._h, lead[0], lead[1], pm, pt, self._array_ptr(points), npts, self._array_ptr(ranges),
+                                                 self._array_ptr(xy), self._array_ptr(strength), L.MEM_DEVICE if dev else L.MEM_HOST),
+                    "cvs_chain_refine_batch")
+        self._refine_keepalive = (points, ranges, keep, ths)
+        if back and out is None:
+            xy, strength = torch.from_numpy(xy), torch.from_numpy(strength)
+        return xy, strength
+
+    def contour_edgels_batch(self, frames, low, high, min_area=0, min_peak=0.0, eps=None):
+        """The linked contours of n same-size frames as sub-pixel edgels, without a loop over frames or planes:
+        pipeline_batch(outputs=[5, 6, 7]) -> nonmax_batch -> link -> contour_chains_batch -> chain_refine_batch -> chain_measures, and
+        chain_polylines(..., return_index=True) when eps is given.  low, high, min_area, min_peak as in contours_batch.  Returns
+        (points, chains, ranges, xy, strength, measures[, vertices, polylines, index]); plane z = 3 * frame + (0 edges, 1 dark lines,
+        2 bright lines), and chains[:, 3] names it.  The object then holds the state of all n frames."""
+        self._caller_check("contour_edgels_batch")
+        if min_area == 0 and min_peak == 0.0:
+            min_peak = -np.inf
+        maps = self.pipeline_batch(frames, outputs=[5, 6, 7])
+        thin = self.nonmax_batch(maps)
+        if not (_is_torch(thin) or isinstance(thin, np.ndarray)):
+            thin = [m for fr in thin for m in fr]
+        else:
+            thin = thin.reshape((-1,) + tuple(thin.shape[2:]))
+        masks = self.link(thin, low, high, min_area=min_area, min_peak=min_peak)
+        points, chains, ranges = self.contour_chains_batch(masks)
+        xy, strength = self.chain_refine_batch(points, ranges, maps)
+        measures = self.chain_measures(points, chains, strength=strength, xy=xy)
+        if eps is None:
+            return points, chains, ranges, xy, strength, measures
+        return (points, chains, ranges, xy, strength, measures) + tuple(self.chain_polylines(points, chains, eps, return_index=True))
+
     def set_persist(self, on):
         """pipeline()/pipeline_batch(): keep the basis + orientation planes (default, like the reference
         object) or write the requested outputs only"""

@@ -2,7 +2,7 @@
 // Internal: cvs_api.cpp (entry points, do_setup), cvs_pipeline.cpp (caller pipeline, 8-bit routes), cvs_handle.cpp (argument checks,
 // staging arena, state blocks), cvs_tune.cpp (launch configuration), cvs_host.cpp (overlapped host path); cvs_layout.h (how planes lie
 // in memory) stands apart: no handle, no device.  The contour tail (cvs_contour.cpp: thinning; cvs_components.cpp, cvs_link.cpp,
-// cvs_chains.cpp, cvs_polyline.cpp, cvs_refine.cpp) adds the helpers of cvs_contour_host.h on top.  The public boundary is include/cvsteer_hip.h.
+// cvs_chains.cpp, cvs_chains_batch.cpp, cvs_polyline.cpp, cvs_refine.cpp) adds the helpers of cvs_contour_host.h on top.  The public boundary is include/cvsteer_hip.h.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -62,7 +62,7 @@ struct cvs_context {
     // partials, tables and point lists in staging; grown only, freed by cvs_destroy
     unsigned char* cc_scr = nullptr;
     size_t cc_scr_bytes = 0;
-    // contour chains (cvs_contour_chains): the arc arrays, sized by an arc count read back while the planes of that call still live in cc_scr
+    // contour chains (cvs_contour_chains, cvs_contour_chains_batch): the arc arrays, sized by an arc count read back while the planes of that call still live in cc_scr
     // (growing cc_scr would lose them), and the staging of host lists; grown only, freed by cvs_destroy
     unsigned char* ch_scr = nullptr;
     size_t ch_scr_bytes = 0;

@@ -522,6 +522,66 @@ int cvs_nonmax_batch(cvs_handle h, int frames, int n_maps, const cvs_plane* thet
 int cvs_contours_batch(cvs_handle h, const cvs_plane* images, int n, float low, float high, int min_area, float min_peak,
                        const cvs_plane* outs);
 
+/* ---- EXTENSION beyond the reference: contour chains and sub-pixel chain points on the batch axis ----
+ * cvs_contour_chains_batch lists the chains of n masks -- the [n][3] masks of cvs_contours_batch, say -- in one launch sequence with one
+ * read-back; its point list and chain table go through cvs_chain_polylines and cvs_chain_measures as they are (neither needs an image, and
+ * neither reads `reserved`), and through cvs_chain_refine_batch, which finds the plane of every point in the range table. */
+
+/* EXTENSION: cvs_contour_chains for n >= 1 masks of the handle's image size at once.  masks: f32 or CVS_DEPTH_U8 planes (they may differ in
+ * depth), pitched or dense, at one constant stride or not, ALL on the device or ALL on the host; foreground as in cvs_label.
+ * The result is the concatenation over z = 0 .. n - 1 of what cvs_contour_chains writes for masks[z] alone: (x, y) are coordinates inside
+ * the plane, chains[c].start is global -- the running sum of the lengths over all planes --, and chains[c].reserved is the plane z (a table
+ * of cvs_contour_chains itself keeps 0 there).  Stated on its own: with LIN(z, p) = z * rows * cols + lin(p), links, nodes, chains,
+ * direction and order are those of the cvs_contour_chains contract with LIN in place of lin, and no link joins pixels of different planes.
+ * The chains and the points of a plane are therefore contiguous ranges: ranges[2 * z] is the index of the first chain of plane z,
+ * ranges[2 * z + 1] that of its first point, entry n holds the totals, and an empty plane repeats its successor's pair (2 * (n + 1) ints).
+ * points, chains and ranges are all in host or all in device memory (mem), whatever memory the masks are in.  *n_points and *n_chains
+ * (both required) are always set; when either exceeds its capacity the call returns CVS_E_SIZE and writes no point, no chain and no range
+ * (points = chains = ranges = NULL with both capacities 0 sizes the buffers).  ranges is written by every call that passes it and fits.
+ * One read-back per call -- the four counters every size follows from --, whatever n is: synchronises the handle's stream,
+ * CVS_E_UNSUPPORTED while it is being captured, CVS_E_STATE before the first setup.  CVS_E_SIZE: a plane of another size, or
+ * n * rows * cols > 2^28 (32 frames x 3 maps x 1920 x 1080 = 199 065 600 fits).  CVS_E_BADARG: n < 1, masks of mixed memory, a NULL array
+ * with a capacity > 0, a negative capacity, a pointer not aligned to 4 bytes, ranges NULL with a capacity > 0, an output that overlaps a mask
+ * or another output.  Nothing is written when an argument is rejected.
+ * The launch sequence depends on (rows, cols, n), on whether the planes lie at one constant stride (an [N, H, W] block, staged host
+ * planes: addressed arithmetically) or not (a device table that launches fill from their arguments, 16 planes each), and on ceil(log2) of
+ * the number of directed links -- never on what the masks hold.  The planes are labelled as one stacked block of n * rows rows that no
+ * link and no union crosses a seam of, so every launch but the links, the labelling, the table and the emit is that of cvs_contour_chains
+ * on that block.
+ * Device memory: 10 bytes per pixel of ALL n planes and 24 bytes per directed link, in the handle scratch of cvs_contour_chains (grown
+ * only, freed by cvs_destroy) -- 2.0 GB before the links for the 96 masks of 32 frames of 1920 x 1080. */
+int cvs_contour_chains_batch(cvs_handle h, int n, const cvs_plane* masks,
+                             int32_t* points, int point_capacity,     /* (x, y) int32 pairs, plane-local */
+                             cvs_chain* chains, int chain_capacity,   /* start global, reserved = plane */
+                             int32_t* ranges,                         /* 2 * (n + 1) ints */
+                             int mem,                                 /* CVS_MEM_HOST / CVS_MEM_DEVICE: the three arrays */
+                             int* n_points, int* n_chains);           /* both required, always set */
+
+/* EXTENSION: cvs_chain_refine for the point list of cvs_contour_chains_batch.  maps: frames * n_maps (n_maps in 1..3) f32 planes of the
+ * handle's image size, frame-major -- the UN-THINNED responses the masks came from; theta: `frames` planes, or NULL = the CVS_PLANE_THETA
+ * state plane of frames 0 .. frames - 1 of the last cvs_pipeline_batch, as in cvs_nonmax_batch (CVS_E_STATE if the handle holds fewer
+ * frames, or no orientation state).  ranges: the table cvs_contour_chains_batch wrote for n = frames * n_maps planes.
+ * Per point i: the cvs_chain_refine contract, operation for operation, on plane z(i) = the largest z in 0 .. n - 1 with
+ * ranges[2 * z + 1] <= i; the samples come from maps[z], theta from theta[z / n_maps].  Every xy and strength value is bit for bit that of
+ * cvs_chain_refine(maps[z], theta[z / n_maps]) on the points of plane z.
+ * points, ranges, xy and strength (may be NULL) are all in host or all in device memory (mem).  One launch, one lane per point; nothing
+ * is read back: asynchronous and capturable with device arrays and device planes (planes at no constant stride need a descriptor table
+ * in handle scratch; under capture that scratch must already have its size, which the same call made once eagerly sees to -- otherwise
+ * CVS_E_UNSUPPORTED, and the handle works on).  Host arrays and host planes are staged, the call synchronises, and it is refused during
+ * capture.
+ * Device data is trusted for its meaning only: z(i) comes from a binary search that cannot leave 0 .. n - 1 whatever `ranges` holds,
+ * coordinates are compared with cols / rows (unsigned) before any load, and a point outside the image stores NaN in xs, ys and strength
+ * and reads no plane -- so no load leaves a plane.  A HOST ranges whose point column is not non-decreasing from 0 to n_points, and a
+ * HOST point outside the image: CVS_E_BADARG before anything is queued.  CVS_E_BADARG as well: frames < 1, n_maps outside 1..3, maps NULL;
+ * every other error as in cvs_chain_refine (points, ranges or xy NULL with n_points > 0 included).  n_points == 0: CVS_OK, nothing
+ * queued.  Nothing is written when an argument is rejected. */
+int cvs_chain_refine_batch(cvs_handle h, int frames, int n_maps,
+                           const cvs_plane* maps,      /* frames * n_maps f32 planes, frame-major */
+                           const cvs_plane* theta,     /* frames planes, or NULL */
+                           const int32_t* points, int n_points,
+                           const int32_t* ranges,      /* as cvs_contour_chains_batch writes it, n = frames * n_maps */
+                           float* xy, float* strength, int mem);
+
 /* the whole caller sequence of test/test.cpp:85-90 / example/steer.cpp:86-90 for one image:
  * setup(FULL) -> steer(theta_dom, g2,h2,e,mag,phase) -> find*(mag|e, phase).
  * outs[8] = {g2, h2, e, magnitude, phase, edges, dark, bright}; any entry may be NULL.
