@@ -613,7 +613,7 @@ class _CallerPipeline:
         pl = _plane(labels)
         n = C.c_int(0)
         rc = lib().cvs_contour_points(self._h, C.byref(pl), None, 0, L.MEM_HOST, C.byref(n))
-        if rc != L.E_SIZE:
+        if not (rc == L.E_SIZE and n.value):   # (E_SIZE with a count: the sizing answer; without one: a plane of another size)
             self._check(rc, "cvs_contour_points")
         dev = _is_torch(labels) and labels.is_cuda
         if dev:
@@ -653,7 +653,7 @@ class _CallerPipeline:
         pm = _plane(mask)
         n, m = C.c_int(0), C.c_int(0)
         rc = lib().cvs_contour_chains(self._h, C.byref(pm), None, 0, None, 0, L.MEM_HOST, C.byref(n), C.byref(m))
-        if rc != L.E_SIZE:
+        if not (rc == L.E_SIZE and (n.value or m.value)):   # (E_SIZE with counts: the sizing answer; without: a plane of another size)
             self._check(rc, "cvs_contour_chains")
         dev = _is_torch(mask) and mask.is_cuda
         if dev:
@@ -1002,7 +1002,7 @@ class _CallerPipeline:
         dev = _is_torch(first) and first.is_cuda
         np_, nc = C.c_int(0), C.c_int(0)
         rc = lib().cvs_contour_chains_batch(self._h, n, pm, None, 0, None, 0, None, L.MEM_HOST, C.byref(np_), C.byref(nc))
-        if rc != L.E_SIZE:
+        if not (rc == L.E_SIZE and (np_.value or nc.value)):   # (E_SIZE with counts: the sizing answer; without: a plane of another size)
             self._check(rc, "cvs_contour_chains_batch")
         if dev:
             pts = torch.empty((np_.value, 2), dtype=torch.int32, device=first.device)

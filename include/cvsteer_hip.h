@@ -220,9 +220,17 @@ int cvs_setup_steer(cvs_handle h, const cvs_plane* image, unsigned flags, float 
 
 /* cvs_setup restricted to the output rows [row_lo, row_hi) of the image: the band one GPU takes when a single large
  * image (a pyramid level, BASELINE config 3) is split over several GPUs.  The whole image must be
- * present (the rows around the band are read, the image borders reflect as usual); state rows outside the band keep
- * whatever they held.  Values inside the band are bit-identical to those of a whole-image cvs_setup.  Images that
- * take the generic path (non-default taps, tiny images) are filtered whole. */
+ * present (the rows around the band are read, the image borders reflect as usual).  Values inside the band are
+ * bit-identical to those of a whole-image cvs_setup with the same flags.  Images that take the generic path (non-default
+ * taps, tiny images) are filtered whole.
+ * ROWS OUTSIDE THE BAND keep, bit for bit, what they held -- so that bands add up to a whole image -- when the handle's
+ * previous state-establishing call was a cvs_setup / cvs_setup_steer / cvs_setup_pyr / cvs_setup_rows of an image of the
+ * same size, with the same flags, and CVS_OPT_STATE_LAYOUT has not been changed since.  After anything else (a fresh
+ * handle, another size, other flags, a cvs_pipeline* call, a changed layout option) the engine may lay the planes out
+ * anew for this call (CVS_OPT_STATE_LAYOUT: the grouping follows the flags), and the rows outside the band are
+ * UNSPECIFIED until bands or a whole-image call have written them; the rows of the band are valid in every case.
+ * The state flags afterwards are those of this call's flags (a basis-only band leaves no orientation state); the handle
+ * holds one frame, frame 0 selected. */
 int cvs_setup_rows(cvs_handle h, const cvs_plane* image, unsigned flags, int row_lo, int row_hi);
 
 /* device view of a state plane (zero copy; valid until the handle's next cvs_setup* / cvs_pipeline* call: the engine may
