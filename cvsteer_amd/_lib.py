@@ -61,6 +61,15 @@ class ChainMeasure(C.Structure):
                 ("peak", C.c_float), ("weakest", C.c_float), ("sum", C.c_double), ("length", C.c_double)]
 
 
+PEAKS_MAX = 4
+
+
+class PeaksCfg(C.Structure):
+    """struct cvs_peaks_cfg"""
+    _fields_ = [("struct_size", C.c_uint32), ("n_angles", C.c_int32), ("max_peaks", C.c_int32), ("min_energy", C.c_float),
+                ("min_ratio", C.c_float), ("min_contrast", C.c_float)]
+
+
 _PP = C.POINTER(Plane)
 _FP = C.POINTER(C.c_float)
 _IP = C.POINTER(C.c_int)
@@ -93,6 +102,7 @@ SIGNATURES = {
     "cvs_steer_scalar": (C.c_int, [C.c_void_p, C.c_float, _PP, _PP, _PP, _PP, _PP]),
     "cvs_steer_map": (C.c_int, [C.c_void_p, _PP, _PP, _PP, _PP, _PP, _PP]),
     "cvs_steer_bank": (C.c_int, [C.c_void_p, _FP, C.c_int, _PP]),
+    "cvs_orientation_peaks": (C.c_int, [C.c_void_p, C.POINTER(PeaksCfg), _PP, _PP, _PP]),
     "cvs_steer_point": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, _FP]),
     "cvs_mag_phase": (C.c_int, [C.c_void_p, _PP, _PP, _PP, _PP]),
     "cvs_wrap": (C.c_int, [C.c_void_p, _PP, _PP]),

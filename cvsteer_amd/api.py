@@ -338,6 +338,32 @@ class SteerableFilters:
         self._check(lib().cvs_steer_bank(self._h, th.ctypes.data_as(C.POINTER(C.c_float)), n, planes), "cvs_steer_bank")
         return tuple(out)
 
+    def orientation_peaks(self, n_angles=16, max_peaks=2, min_energy=0.0, min_ratio=0.25, min_contrast=1e-3, out=None):
+        """every local orientation of each pixel (cvs_orientation_peaks): the oriented energy g^2 + h^2 at n_angles angles k pi / K, its
+        circular local maxima refined by a parabola, the max_peaks strongest kept -- one pass over the basis planes.
+        Returns (angles[M, H, W], energies[M, H, W], count[H, W] uint8): slot 0 is the strongest peak, slots from count upward hold
+        angle -1 and energy 0.  An angle theta is the steering angle: the direction across the structure is (cos theta, -sin theta)
+        in (column, row) steps, so a ridge of direction phi peaks at phi + pi / 2 (mod pi).
+        out: (angles, energies, count), any of them None = not written (and returned as None)."""
+        M = int(max_peaks)
+        if out is None:
+            shape = tuple(self.shape)
+            blk = self._new((2, M) + shape) if 1 <= M <= L.PEAKS_MAX else self._new((2, 1) + shape)   # (the library refuses M)
+            cnt = torch.empty(shape, dtype=torch.uint8, device=blk.device) if _is_torch(blk) else np.empty(shape, np.uint8)
+            out = (blk[0], blk[1], cnt)
+        ang, en, cnt = out
+        if ang is None and en is None and cnt is None:
+            raise ValueError("out: at least one of (angles, energies, count)")
+        if 1 <= M <= L.PEAKS_MAX and any(x is not None and len(x) != M for x in (ang, en)):
+            raise ValueError("out: angles and energies hold max_peaks planes each")
+        cfg = L.PeaksCfg(C.sizeof(L.PeaksCfg), int(n_angles), M, float(min_energy), float(min_ratio), float(min_contrast))
+        pa = _planes(list(ang)) if ang is not None else None
+        pe = _planes(list(en)) if en is not None else None
+        pc = _plane(cnt) if cnt is not None else None
+        self._bind_stream(*([] if ang is None else list(ang)), *([] if en is None else list(en)), cnt)
+        self._check(lib().cvs_orientation_peaks(self._h, C.byref(cfg), pa, pe, C.byref(pc) if pc is not None else None),
+                    "cvs_orientation_peaks")
+        return ang, en, cnt
 
     # -- adjacent component (SURVEY 8f): Gaussian pyramid, not part of the reference --
     def pyrDown(self, image):

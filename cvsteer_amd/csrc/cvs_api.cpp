@@ -198,6 +198,27 @@ int cvs::need_state(cvs_handle h, bool orient)
     return CVS_OK;
 }
 
+// the state planes a bank launch reads, as groups at a constant stride (BankArgs::in: basis | C1..C3, or g4 | h4 | C1..C3; C1..C3 only
+// with `e`); false = the layout does not allow it.  cvs_peaks.cpp reads the basis groups the same way
+bool cvs::bank_inputs(cvs_handle h, bool e, BankPlane in[3])
+{
+    const int nb = h->nb, split = nb == 7 ? 7 : 5;
+    const int first[3] = {0, split, nb}, count[3] = {split, nb - split, 3};
+    const int ng = (nb == 7 ? 1 : 2) + (e ? 1 : 0);
+    for (int g = 0; g < 3; ++g) in[g] = {nullptr, 0, 0};
+    for (int g = 0; g < ng; ++g) {
+        const int f = g == ng - 1 && e ? nb : first[g], m = g == ng - 1 && e ? 3 : count[g];
+        const PlaneRef p0 = state_ref(h, f);
+        const size_t stride = m > 1 ? (size_t)(state_plane(h, f + 1) - p0.p) : 0;
+        for (int j = 1; j < m; ++j) {
+            const PlaneRef pj = state_ref(h, f + j);
+            if (pj.p != p0.p + (size_t)j * stride || pj.pitch != p0.pitch) return false;
+        }
+        in[g] = {p0.p, p0.pitch, stride};
+    }
+    return true;
+}
+
 namespace {
 
 void basis_inputs(cvs_handle h, PointArgs& a)
@@ -609,26 +630,6 @@ int cvs_steer_map(cvs_handle h, const cvs_plane* theta, const cvs_plane* g, cons
     return steer_common(h, true, 0.f, theta, g, hq, e, mag, phase);
 }
 
-// the state planes a bank launch reads, as groups at a constant stride (BankArgs::in); false = the layout does not allow it
-static bool bank_inputs(cvs_handle h, bool e, BankArgs& a)
-{
-    const int nb = h->nb, split = nb == 7 ? 7 : 5;
-    const int first[3] = {0, split, nb}, count[3] = {split, nb - split, 3};
-    const int ng = (nb == 7 ? 1 : 2) + (e ? 1 : 0);
-    for (int g = 0; g < 3; ++g) a.in[g] = {nullptr, 0, 0};
-    for (int g = 0; g < ng; ++g) {
-        const int f = g == ng - 1 && e ? nb : first[g], m = g == ng - 1 && e ? 3 : count[g];
-        const PlaneRef p0 = state_ref(h, f);
-        const size_t stride = m > 1 ? (size_t)(state_plane(h, f + 1) - p0.p) : 0;
-        for (int j = 1; j < m; ++j) {
-            const PlaneRef pj = state_ref(h, f + j);
-            if (pj.p != p0.p + (size_t)j * stride || pj.pitch != p0.pitch) return false;
-        }
-        a.in[g] = {p0.p, p0.pitch, stride};
-    }
-    return true;
-}
-
 static void bank_angle(cvs_handle h, BankArgs& a, int t, float theta)
 {
     host_steer_weights(h->kind, theta, a.w[t]);
@@ -671,7 +672,7 @@ int cvs_steer_bank(cvs_handle h, const float* thetas, int n, const cvs_plane* ou
     a.atan_mode = h->atan_mode;
     a.nt_stores = use_nt_stores(h, (size_t)a.rows * a.cols);
     a.nt_loads = a.nt_stores;   // as cvs_steer_scalar: the state planes of an image that large are not cache-resident
-    if (!bank_inputs(h, want[2], a)) return fail(h, CVS_E_STATE, "state planes not at a constant stride within their group");
+    if (!bank_inputs(h, want[2], a.in)) return fail(h, CVS_E_STATE, "state planes not at a constant stride within their group");
 
     // one launch per kBankMax angles when every written plane is a device plane and each kind's planes lie at one pitch and a
     // constant stride (a [K][H][W] or [H][K][W] block, what the Python side allocates)

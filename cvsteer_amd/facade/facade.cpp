@@ -504,6 +504,54 @@ void SteerableFiltersG2::steer(const std::vector<float>& thetas, std::vector<Mat
     check(steer_bank_views(m_handle, thetas, outs), "cvs_steer_bank");
 }
 
+// cvs_orientation_peaks into host planes allocated as the Mat1f& overloads allocate theirs; the count plane stays here and only its
+// largest byte is returned.  Status, or that number through *n
+namespace {
+int orientation_peaks(cvs_handle h, std::vector<Mat1f>& angles, std::vector<Mat1f>& energies, int nAngles, int maxPeaks, float minEnergy,
+                      float minRatio, float minContrast, int* n)
+{
+    int rows = 0, cols = 0;
+    int rc = cvs_shape(h, &rows, &cols);
+    if (rc != CVS_OK) return rc;
+    cvs_peaks_cfg cfg;
+    cfg.struct_size = (unsigned)sizeof(cfg);
+    cfg.n_angles = nAngles;
+    cfg.max_peaks = maxPeaks;
+    cfg.min_energy = minEnergy;
+    cfg.min_ratio = minRatio;
+    cfg.min_contrast = minContrast;
+    const size_t m = maxPeaks >= 1 && maxPeaks <= CVS_PEAKS_MAX && rows > 0 ? (size_t)maxPeaks : 0;   // (the library refuses the rest)
+    std::vector<cvs_plane> pa(m), pe(m);
+    angles.resize(m);
+    energies.resize(m);
+    for (size_t s = 0; s < m; ++s) {
+        pa[s] = out_view(angles[s], rows, cols);
+        pe[s] = out_view(energies[s], rows, cols);
+    }
+    std::vector<unsigned char> count((size_t)rows * (size_t)cols);
+    cvs_plane pc;
+    pc.data = reinterpret_cast<float*>(count.data());
+    pc.rows = rows;
+    pc.cols = cols;
+    pc.step = (size_t)cols;
+    pc.mem = CVS_MEM_HOST | CVS_DEPTH_U8;
+    rc = cvs_orientation_peaks(h, &cfg, m ? pa.data() : 0, m ? pe.data() : 0, &pc);
+    if (rc != CVS_OK) return rc;
+    unsigned char most = 0;
+    for (size_t i = 0; i < count.size(); ++i) most = count[i] > most ? count[i] : most;
+    *n = (int)most;
+    return CVS_OK;
+}
+}  // namespace
+
+int SteerableFiltersG2::orientationPeaks(std::vector<Mat1f>& angles, std::vector<Mat1f>& energies, int nAngles, int maxPeaks, float minEnergy,
+                                         float minRatio, float minContrast)
+{
+    int n = 0;
+    check(orientation_peaks(m_handle, angles, energies, nAngles, maxPeaks, minEnergy, minRatio, minContrast, &n), "cvs_orientation_peaks");
+    return n;
+}
+
 // --------------------------------------------------------------------------- G4
 SteerableFiltersG4::SteerableFiltersG4(const Mat1f& image, int width, float spacing)
     : SteerableFilters(CVS_KIND_G4, width, spacing, 0)
@@ -604,6 +652,14 @@ void SteerableFiltersG4::steer(const std::vector<float>& thetas, std::vector<Mat
 {
     std::vector<Mat1f>* const outs[5] = {&g4, &h4, 0, 0, 0};
     check(steer_bank_views(m_handle, thetas, outs), "cvs_steer_bank");
+}
+
+int SteerableFiltersG4::orientationPeaks(std::vector<Mat1f>& angles, std::vector<Mat1f>& energies, int nAngles, int maxPeaks, float minEnergy,
+                                         float minRatio, float minContrast)
+{
+    int n = 0;
+    check(orientation_peaks(m_handle, angles, energies, nAngles, maxPeaks, minEnergy, minRatio, minContrast, &n), "cvs_orientation_peaks");
+    return n;
 }
 
 void SteerableFiltersG4::computeMagnitudeAndPhase(const Mat1f&, const Mat1f&, Mat1f&, Mat1f&) {}

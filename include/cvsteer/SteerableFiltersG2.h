@@ -53,6 +53,12 @@ public:
     void steer(const std::vector<float>& thetas, std::vector<Mat1f>& g2, std::vector<Mat1f>& h2);
     void steer(const std::vector<float>& thetas, std::vector<Mat1f>& g2, std::vector<Mat1f>& h2, std::vector<Mat1f>& e,
                std::vector<Mat1f>& magnitude, std::vector<Mat1f>& phase);
+    // orientation peaks (extension, cvs_orientation_peaks): every local orientation of each pixel from one read of the basis planes --
+    // the oriented energy at nAngles angles, its circular local maxima refined, the maxPeaks strongest kept.  angles / energies are
+    // resized to maxPeaks planes, slot 0 the strongest; slots a pixel does not fill hold angle -1 and energy 0.  A ridge of direction
+    // phi peaks at phi + pi/2 (mod pi).  Returns the largest number of peaks any pixel has.
+    int orientationPeaks(std::vector<Mat1f>& angles, std::vector<Mat1f>& energies, int nAngles = 16, int maxPeaks = 2, float minEnergy = 0.f,
+                         float minRatio = 0.25f, float minContrast = 1e-3f);
     // contour thinning (extension): non-maximum suppression of `response` across the dominant orientation m_theta (cvs_nonmax), and
     // 8-connected hysteresis with output 0 / 255 as floats (cvs_hysteresis) -- the callers' convertTo(CV_8UC1) applies unchanged
     void nonMaxSuppression(const Mat1f& response, Mat1f& output);

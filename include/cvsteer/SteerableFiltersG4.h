@@ -30,6 +30,9 @@ public:
     void getBasis(int index, Mat1f& dst) const;
     // addition: steer(thetas[k], g4[k], h4[k]) for every angle from one read of the basis planes (cvs_steer_bank)
     void steer(const std::vector<float>& thetas, std::vector<Mat1f>& g4, std::vector<Mat1f>& h4);
+    // addition: orientation peaks, as in SteerableFiltersG2 (cvs_orientation_peaks): the G4 / H4 pair separates arms the G2 / H2 pair blurs
+    int orientationPeaks(std::vector<Mat1f>& angles, std::vector<Mat1f>& energies, int nAngles = 16, int maxPeaks = 2, float minEnergy = 0.f,
+                         float minRatio = 0.25f, float minContrast = 1e-3f);
     // addition: contour components, as in SteerableFiltersG2 (cvs_contour_prune / cvs_label; they read the planes passed, not the object's state)
     int pruneContours(const Mat1f& mask, const Mat1f& weight, int minArea, float minPeak, Mat1f& out);
     // addition: hysteresis and pruneContours(that, response, ...) in one labelling, as in SteerableFiltersG2 (cvs_link)

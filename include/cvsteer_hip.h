@@ -267,6 +267,51 @@ int cvs_steer_bank(cvs_handle h, const float* thetas, int n, const cvs_plane* ou
  * out = {g2, h2, e, magnitude, phase}; e is NaN when orientation state is absent. */
 int cvs_steer_point(cvs_handle h, int x, int y, float theta, float out[5]);
 
+/* ---- EXTENSION beyond the reference: orientation peaks -- every local orientation of a pixel, from one read of the basis planes ----
+ * The oriented energy E(theta) = g(theta)^2 + h(theta)^2 of the handle's quadrature pair is sampled at K angles per pixel, its circular
+ * local maxima are found, refined by a parabola through three samples, and the M strongest are written: the arms of a crossing, a corner
+ * or a T, which the single dominant angle of C1..C3 cannot hold.  Reads the basis planes of the frame chosen by cvs_select_frame
+ * (CVS_E_STATE without basis state); needs no orientation state and no CVS_OPT_G4_EXTENSIONS; G2 and G4 handles, every state layout,
+ * and the state a cvs_pipeline* call left behind.
+ * Geometry: theta is the reference's steering angle.  The direction ACROSS the structure, in (column, row) steps, is (cos theta,
+ * -sin theta) -- the convention of cvs_nonmax --, so a straight ridge or edge of direction phi peaks at phi + pi/2 (mod pi).
+ * Contract, per pixel; every operation is an f32 operation that rounds on its own, the division is correctly rounded:
+ *  1. theta_k = (float)((double)k * pi / K), k = 0 .. K-1; (g_k, h_k) are bit for bit what cvs_steer_scalar(h, theta_k, ...) writes.
+ *  2. e_k = g_k*g_k + h_k*h_k.
+ *  3. emax / emin = the largest / smallest e_k.
+ *  4. A pixel with an e_k that is not finite has no peaks; nor has one unless emax - emin > min_contrast * emax.
+ *  5. k is a candidate when e_k > e_(k-1) && e_k >= e_(k+1), indices mod K (the plateau rule of cvs_nonmax: one sample of a two-sample
+ *     plateau survives), and e_k > min_energy and e_k >= min_ratio * emax.
+ *  6. Candidates are ordered by e_k descending, ties by smaller k; the first M are kept.
+ *  7. count = min(number of candidates, M).
+ *  8. For a kept k, with p = e_(k-1), c = e_k, n = e_(k+1):  num = p - n;  den = (p - 2c) + n;  d = den < 0 ? (0.5*num) / den : 0, then
+ *     d = min(max(d, -0.5), 0.5);  angle = ((float)k + d) * (float)(pi / K), plus (float)pi if it is below 0, then minus (float)pi if it is
+ *     not below (float)pi -- so angle lies in [0, (float)pi);  energy = c - (0.25*num)*d.
+ *  9. Slots from count upward store angle -1.0f and energy 0.0f.
+ * angles / energies: NULL, or max_peaks f32 planes each, slot 0 = the strongest peak; count: NULL, or one CVS_DEPTH_U8 plane.  Any
+ * non-empty subset may be asked for, and each plane written holds the values of the full call.
+ * CVS_E_BADARG: cfg NULL, a struct_size that is not sizeof(cvs_peaks_cfg), n_angles outside 4 .. 32, max_peaks outside 1 ..
+ * CVS_PEAKS_MAX, a threshold that is NaN, min_ratio or min_contrast outside [0, 1], all three outputs NULL, a plane of the wrong depth,
+ * an output that overlaps another output or a state plane of the selected frame.  A plane of another size than the handle's image:
+ * CVS_E_SIZE.  Nothing is written when an argument is refused.
+ * Host and device planes, any row step.  Device planes whose slots share a step and follow one another at a constant distance (a
+ * [max_peaks][rows][cols] block) take ONE kernel launch, asynchronous on the handle's stream and capturable; nothing
+ * is read back.  Host planes, and device planes placed otherwise, are written through the handle's staging arena by the same launch
+ * (CVS_E_UNSUPPORTED while the stream is being captured); with a host plane the call returns after the data has landed. */
+#define CVS_PEAKS_MAX 4
+typedef struct cvs_peaks_cfg {
+    unsigned struct_size;   /* sizeof(cvs_peaks_cfg) */
+    int n_angles;           /* K, 4 .. 32 */
+    int max_peaks;          /* M, 1 .. CVS_PEAKS_MAX */
+    float min_energy;       /* a peak needs e_k >  min_energy */
+    float min_ratio;        /* ... and e_k >= min_ratio * emax            (0 .. 1) */
+    float min_contrast;     /* a pixel has peaks only if emax - emin > min_contrast * emax   (0 .. 1) */
+} cvs_peaks_cfg;
+int cvs_orientation_peaks(cvs_handle h, const cvs_peaks_cfg* cfg,
+                          const cvs_plane* angles,    /* NULL, or M f32 planes: slot 0 = strongest */
+                          const cvs_plane* energies,  /* NULL, or M f32 planes */
+                          const cvs_plane* count);    /* NULL, or one CVS_DEPTH_U8 plane */
+
 /* computeMagnitudeAndPhase G2.cpp:107-112 (cartToPolar, wrap, patchNaNs) */
 int cvs_mag_phase(cvs_handle h, const cvs_plane* g, const cvs_plane* hq,
                   const cvs_plane* mag, const cvs_plane* phase);
