@@ -692,8 +692,10 @@ int cvs_normalize_u8(cvs_handle h, const cvs_plane* src, uint8_t* dst, size_t ds
 /* Mat::convertTo(dst, CV_8UC1, alpha, beta) -- the `--gain` branch of example/steer.cpp:92-97 */
 int cvs_convert_u8(cvs_handle h, const cvs_plane* src, float alpha, float beta, uint8_t* dst, size_t dst_step, int dst_mem);
 /* the same for n planes in one go (a driver turning a whole block of feature maps into 8-bit files, steer.cpp:92-122 per
- * file): equally sized device planes at a constant stride take one min/max launch, one quantise launch and one
- * synchronisation for all of them; anything else goes plane by plane.  dst[i] receives plane i. */
+ * file): equally sized device planes at a constant stride take one min/max launch and one quantise launch for all of them;
+ * anything else goes plane by plane.  dst[i] receives plane i.  HOST destinations: the bytes come down behind the launches and the
+ * call synchronises once (plane by plane: once per plane).  DEVICE destinations (and device sources): nothing is read back, the call
+ * is asynchronous on the handle's stream like the single-plane forms above. */
 int cvs_normalize_u8_batch(cvs_handle h, const cvs_plane* src, int n, uint8_t* const* dst, size_t dst_step, int dst_mem);
 int cvs_convert_u8_batch(cvs_handle h, const cvs_plane* src, int n, float alpha, float beta, uint8_t* const* dst, size_t dst_step, int dst_mem);
 
