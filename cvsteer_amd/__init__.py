@@ -6,6 +6,7 @@ this package is the Python host-side mirror of the reference's ``fa::SteerableFi
 works anywhere the library loads, but creating a filter object needs a HIP device.
 """
 from ._lib import CHAIN_CLOSED, CHAIN_HEAD_JUNCTION, CHAIN_TAIL_JUNCTION, CvsError, abi_version, lib, lib_path  # noqa: F401
+from ._lib import SEG_DEGENERATE, SEG_WRAPS  # noqa: F401
 from .api import (  # noqa: F401
     SETUP_BASIS, SETUP_FULL, SETUP_ORIENT, SteerableFilters, SteerableFiltersG2, SteerableFiltersG4,
     KIND_G2, KIND_G4, alloc_planes, basis_taps, make_taps, num_basis, pyramid_setup, steer_weights,
@@ -15,5 +16,5 @@ __all__ = [
     "SteerableFilters", "SteerableFiltersG2", "SteerableFiltersG4", "CvsError", "lib", "lib_path",
     "abi_version", "make_taps", "basis_taps", "num_basis", "steer_weights",
     "SETUP_BASIS", "SETUP_ORIENT", "SETUP_FULL", "KIND_G2", "KIND_G4", "alloc_planes", "pyramid_setup",
-    "CHAIN_CLOSED", "CHAIN_HEAD_JUNCTION", "CHAIN_TAIL_JUNCTION",
+    "CHAIN_CLOSED", "CHAIN_HEAD_JUNCTION", "CHAIN_TAIL_JUNCTION", "SEG_WRAPS", "SEG_DEGENERATE",
 ]

@@ -61,6 +61,13 @@ class ChainMeasure(C.Structure):
                 ("peak", C.c_float), ("weakest", C.c_float), ("sum", C.c_double), ("length", C.c_double)]
 
 
+class Segment(C.Structure):
+    """struct cvs_segment"""
+    _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("chain", C.c_int32), ("flags", C.c_int32)] + \
+               [(name, C.c_double) for name in ("w", "sx", "sy", "sxx", "sxy", "syy", "cx", "cy", "ux", "uy", "t0", "t1", "rms", "dmax")]
+
+
+SEG_WRAPS, SEG_DEGENERATE = 1, 2
 PEAKS_MAX = 4
 
 
@@ -119,6 +126,8 @@ SIGNATURES = {
                                       C.c_void_p, C.c_int, _IP]),
     "cvs_chain_refine": (C.c_int, [C.c_void_p, _PP, _PP, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
     "cvs_chain_measures": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "cvs_polyline_segments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_int]),
     "cvs_contour_chains_batch": (C.c_int, [C.c_void_p, C.c_int, _PP, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, _IP, _IP]),
     "cvs_chain_refine_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _PP, _PP, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_int]),

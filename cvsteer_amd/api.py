@@ -843,6 +843,65 @@ class _CallerPipeline:
         xy, strength = self.chain_refine(points, map, theta)
         return points, chains, xy, strength, self.chain_measures(points, chains, strength=strength, xy=xy)
 
+    # -- contour segments (extension beyond the reference): cvs_polyline_segments --
+    SEGMENT_DTYPE = np.dtype([("first", "<i4"), ("count", "<i4"), ("chain", "<i4"), ("flags", "<i4")] +
+                             [(name, "<f8") for name in ("w", "sx", "sy", "sxx", "sxy", "syy", "cx", "cy", "ux", "uy", "t0", "t1", "rms", "dmax")])
+
+    def polyline_segments(self, points, chains, polylines, index, xy=None, strength=None, out=None):
+        """One record per polyline vertex (cvs_polyline_segments): a numpy structured array with the fields of `cvs_segment` -- record k is
+        the total-least-squares line through the points of the span that starts at vertex k (first, count, chain, flags; the weighted
+        moments w .. syy about the span's first pixel; the line (cx, cy) + t (ux, uy), t in [t0, t1]; rms and dmax, the RMS and largest
+        distance of the points from it); count 0 where no span starts (the last vertex of an open polyline).  points (N, 2) int32 and
+        chains (M, 4) int32 as contour_chains returns them, polylines (M, 4) and index (V,) int32 as chain_polylines(return_index=True)
+        does, xy (N, 2) and strength (N,) float32 as chain_refine does: xy=None fits the integer points, strength=None weighs every point 1.
+        Torch CUDA arrays take the device path: the table is written on the device and downloaded for the return value -- or, with out= a
+        (V, 128) uint8 CUDA tensor, left there (two launches, nothing read back, capturable; out.cpu().numpy().view(SEGMENT_DTYPE) reads
+        it) and `out` is returned.  numpy arrays and torch CPU tensors take the host path.  include/cvsteer_hip.h has the contract."""
+        dev = _is_torch(points) and points.is_cuda
+        points = self._chain_array(points, dev, np.int32, 2, "points")
+        chains = self._chain_array(chains, dev, np.int32, 4, "chains")
+        polylines = self._chain_array(polylines, dev, np.int32, 4, "polylines")
+        index = self._chain_array(index, dev, np.int32, 0, "index")
+        xy = self._chain_array(xy, dev, np.float32, 2, "xy")
+        strength = self._chain_array(strength, dev, np.float32, 0, "strength")
+        n, m, v = int(points.shape[0]), int(chains.shape[0]), int(index.shape[0])
+        if polylines.shape[0] != m:
+            raise ValueError("polylines: one entry per chain")
+        if (strength is not None and strength.shape[0] != n) or (xy is not None and xy.shape[0] != n):
+            raise ValueError("strength and xy: one entry per point")
+        size = self.SEGMENT_DTYPE.itemsize
+        if out is not None:
+            if not (dev and self._is_out(out, dev, np.uint8, (v, size))):
+                raise ValueError("out: a contiguous (V, %d) uint8 CUDA tensor, with device arrays" % size)
+            table = out
+        elif dev:
+            table = torch.empty((v, size), dtype=torch.uint8, device=points.device)
+        else:
+            table = np.zeros(v, self.SEGMENT_DTYPE)
+        if dev:
+            self._bind_stream(points)
+        self._check(lib().cvs_polyline_segments(self._h, self._array_ptr(points), n, self._array_ptr(chains), self._array_ptr(polylines), m,
+                                                self._array_ptr(index), v, self._array_ptr(xy), self._array_ptr(strength),
+                                                self._array_ptr(table), L.MEM_DEVICE if dev else L.MEM_HOST), "cvs_polyline_segments")
+        if out is not None or not dev:
+            return table
+        return table.cpu().numpy().view(self.SEGMENT_DTYPE).reshape(v)
+
+    def contour_segments(self, mask, map, eps, theta=None, weighted=False, min_points=2):
+        """The straight segments of the linked contours of a mask, to sub-pixel accuracy: contour_chains(mask) ->
+        chain_polylines(eps, return_index=True) -> chain_refine on the un-thinned `map` the mask came from -> polyline_segments on the
+        refined positions (weighted=True: weighted by the refined strengths).  Returns (segments, lines): the records with
+        count >= min_points that are not SEG_DEGENERATE, and their (N, 4) float64 end points (cx + t0 ux, cy + t0 uy, cx + t1 ux,
+        cy + t1 uy)."""
+        points, chains = self.contour_chains(mask)
+        _, polylines, index = self.chain_polylines(points, chains, eps, return_index=True)
+        xy, strength = self.chain_refine(points, map, theta)
+        seg = self.polyline_segments(points, chains, polylines, index, xy=xy, strength=strength if weighted else None)
+        seg = seg[(seg["count"] >= min_points) & ((seg["flags"] & L.SEG_DEGENERATE) == 0)]
+        lines = np.stack([seg["cx"] + seg["t0"] * seg["ux"], seg["cy"] + seg["t0"] * seg["uy"],
+                          seg["cx"] + seg["t1"] * seg["ux"], seg["cy"] + seg["t1"] * seg["uy"]], axis=1).reshape(-1, 4)
+        return seg, lines
+
     def contours(self, image, low, high, min_area=0, min_peak=0.0):
         """Thin, linked contours of one image: pipeline(image) -> nonmax(edges, dark, bright) on the object's own theta ->
         hysteresis(low, high).  Returns three uint8 masks (edges, dark lines, bright lines).  min_area > 0 or min_peak > 0: the

@@ -2,7 +2,7 @@
 // Internal: cvs_api.cpp (entry points, do_setup), cvs_pipeline.cpp (caller pipeline, 8-bit routes), cvs_handle.cpp (argument checks,
 // staging arena, state blocks), cvs_tune.cpp (launch configuration), cvs_host.cpp (overlapped host path); cvs_layout.h (how planes lie
 // in memory) stands apart: no handle, no device.  The contour tail (cvs_contour.cpp: thinning; cvs_components.cpp, cvs_link.cpp,
-// cvs_chains.cpp, cvs_chains_batch.cpp, cvs_polyline.cpp, cvs_refine.cpp) adds the helpers of cvs_contour_host.h on top, and cvs_peaks.cpp
+// cvs_chains.cpp, cvs_chains_batch.cpp, cvs_polyline.cpp, cvs_refine.cpp, cvs_segments.cpp) adds the helpers of cvs_contour_host.h on top, and cvs_peaks.cpp
 // (orientation peaks) borrows its checks.  The public boundary is include/cvsteer_hip.h.
 #pragma once
 #include <hip/hip_runtime_api.h>

@@ -209,29 +209,13 @@ __global__ __launch_bounds__(256) void k_measure_wave(const MeasureArgs a)
     if (lane == 0) ms_store(a.table, c, t, acc);
 }
 
-// the long chains of a table: a workgroup takes slices of 256 table entries (slice = blockIdx.x, + gridDim.x, ...), ballots the entries
-// that are longer than kPlWaveMax and calls f(chain index, chain) for each, all 256 lanes together.  lm: four words of LDS.
+// the long chains of a table (ms_long_entries, cvs_refine.h): f(chain index, chain) for each chain longer than kPlWaveMax
 template <class F>
 __device__ __forceinline__ void ms_long_chains(const int32_t* chains, int n_chains, int n_points, unsigned long long* lm, F f)
 {
-    for (long long base = (long long)blockIdx.x * 256; base < n_chains; base += (long long)gridDim.x * 256) {
-        const long long c = base + threadIdx.x;
-        const bool is_long = c < n_chains && ms_chain(chains, c, n_points).len > kPlWaveMax;
-        const unsigned long long b = __ballot(is_long);
-        if ((threadIdx.x & 63) == 0) lm[threadIdx.x >> 6] = b;
-        __syncthreads();
-#pragma unroll 1
-        for (int w = 0; w < 4; ++w) {
-            unsigned long long bits = lm[w];
-            while (bits) {
-                const int k = __ffsll((long long)bits) - 1;
-                bits &= bits - 1;
-                const long long cc = base + w * 64 + k;
-                f(cc, ms_chain(chains, cc, n_points));
-            }
-        }
-        __syncthreads();   // lm is written again
-    }
+    ms_long_entries(
+        n_chains, lm, [&](long long c) { return ms_chain(chains, c, n_points).len > kPlWaveMax; },
+        [&](long long c) { f(c, ms_chain(chains, c, n_points)); });
 }
 
 __global__ __launch_bounds__(256) void k_measure_block(const MeasureArgs a)

@@ -181,6 +181,57 @@ int refine_contours(cvs_handle h, const Mat1f& response, const std::vector<std::
     return CVS_OK;
 }
 
+// approx_contours (with the index), refine_contours on the handle's own theta and cvs_polyline_segments on their results, one packing for
+// the three calls; the host loop only evaluates the end points of the finished records and narrows them to float
+int fit_segments(cvs_handle h, const Mat1f& response, const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags, float eps,
+                 std::vector<std::vector<float> >& lines, std::vector<std::vector<float> >* rms, int* n)
+{
+    if (flags && flags->size() != chains.size()) return CVS_E_BADARG;
+    size_t np = 0;
+    for (size_t c = 0; c < chains.size(); ++c) np += chains[c].size();
+    if (np > (size_t)1 << 30) return CVS_E_SIZE;
+    std::vector<int32_t> pts(np * 2), vtx(np * 2), idx(np);
+    std::vector<float> xy(np * 2);
+    std::vector<cvs_chain> tab(chains.size()), pol(chains.size());
+    size_t at = 0;
+    for (size_t c = 0; c < chains.size(); ++c) {
+        tab[c].start = (int32_t)at;
+        tab[c].length = (int32_t)chains[c].size();
+        tab[c].flags = flags ? (*flags)[c] : 0;
+        tab[c].reserved = 0;
+        for (size_t k = 0; k < chains[c].size(); ++k, ++at) {
+            pts[2 * at] = chains[c][k].x;
+            pts[2 * at + 1] = chains[c][k].y;
+        }
+    }
+    int nv = 0;
+    int rc = cvs_chain_polylines(h, pts.data(), (int)np, tab.data(), (int)chains.size(), eps, vtx.data(), (int)np, idx.data(), pol.data(),
+                                 CVS_MEM_HOST, &nv);
+    if (rc != CVS_OK) return rc;
+    cvs_plane pr = view(response);
+    if ((rc = cvs_chain_refine(h, &pr, 0, pts.data(), (int)np, xy.data(), 0, CVS_MEM_HOST)) != CVS_OK) return rc;
+    std::vector<cvs_segment> seg((size_t)nv);
+    rc = cvs_polyline_segments(h, pts.data(), (int)np, tab.data(), pol.data(), (int)chains.size(), idx.data(), nv, xy.data(), 0, seg.data(),
+                               CVS_MEM_HOST);
+    if (rc != CVS_OK) return rc;
+    lines.assign(chains.size(), std::vector<float>());
+    if (rms) rms->assign(chains.size(), std::vector<float>());
+    int count = 0;
+    for (int k = 0; k < nv; ++k) {
+        const cvs_segment& s = seg[(size_t)k];
+        if (s.count < 2 || (s.flags & CVS_SEG_DEGENERATE)) continue;
+        std::vector<float>& out = lines[(size_t)s.chain];
+        out.push_back((float)(s.cx + s.t0 * s.ux));
+        out.push_back((float)(s.cy + s.t0 * s.uy));
+        out.push_back((float)(s.cx + s.t1 * s.ux));
+        out.push_back((float)(s.cy + s.t1 * s.uy));
+        if (rms) (*rms)[(size_t)s.chain].push_back((float)s.rms);
+        ++count;
+    }
+    *n = count;
+    return CVS_OK;
+}
+
 }  // namespace
 
 // --------------------------------------------------------------------------- base
@@ -448,6 +499,14 @@ int SteerableFiltersG2::refineContours(const Mat1f& response, const std::vector<
     return n;
 }
 
+int SteerableFiltersG2::fitSegments(const Mat1f& response, const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags,
+                                    float epsilon, std::vector<std::vector<float> >& lines, std::vector<std::vector<float> >* rms)
+{
+    int n = 0;
+    check(fit_segments(m_handle, response, chains, flags, epsilon, lines, rms, &n), "cvs_polyline_segments");
+    return n;
+}
+
 void SteerableFiltersG2::phaseWeights(const Mat1f& phase, Mat1f& lambda, float phi, bool signum, float k)
 {
     std::lock_guard<std::mutex> lock(g_static_mutex);
@@ -606,6 +665,14 @@ int SteerableFiltersG4::refineContours(const Mat1f& response, const std::vector<
 {
     int n = 0;
     check(refine_contours(m_handle, response, chains, xs, ys, strength, &n), "cvs_chain_refine");
+    return n;
+}
+
+int SteerableFiltersG4::fitSegments(const Mat1f& response, const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags,
+                                    float epsilon, std::vector<std::vector<float> >& lines, std::vector<std::vector<float> >* rms)
+{
+    int n = 0;
+    check(fit_segments(m_handle, response, chains, flags, epsilon, lines, rms, &n), "cvs_polyline_segments");
     return n;
 }
 

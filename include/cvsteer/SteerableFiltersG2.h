@@ -86,6 +86,13 @@ public:
     // Returns the number of points
     int refineContours(const Mat1f& response, const std::vector<std::vector<Point> >& chains, std::vector<std::vector<float> >& xs,
                        std::vector<std::vector<float> >& ys, std::vector<std::vector<float> >* strength = 0);
+    // contour segments (extension, cvs_polyline_segments): the straight segments of the chains to sub-pixel accuracy -- approxContours
+    // with tolerance `epsilon`, refineContours on `response`, and the total-least-squares line through the refined points of every polyline
+    // span, by the contract of include/cvsteer_hip.h.  lines[c] = four floats x0 y0 x1 y1 per span of chains[c] that is not degenerate, in
+    // span order (narrowed from double); rms (optional): rms[c] = one float per such span, its RMS distance from the line.  flags as in
+    // approxContours.  Returns the number of segments
+    int fitSegments(const Mat1f& response, const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags, float epsilon,
+                    std::vector<std::vector<float> >& lines, std::vector<std::vector<float> >* rms = 0);
 
 protected:
     // the reference's protected members, same names (SteerableFiltersG2.h:62-66).  m_g1..m_h4 are the 7 tap vectors; the

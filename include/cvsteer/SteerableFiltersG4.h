@@ -47,6 +47,10 @@ public:
     // no orientation state)
     int refineContours(const Mat1f& response, const std::vector<std::vector<Point> >& chains, std::vector<std::vector<float> >& xs,
                        std::vector<std::vector<float> >& ys, std::vector<std::vector<float> >* strength = 0);
+    // addition: sub-pixel line fits of the polyline spans, as in SteerableFiltersG2 (cvs_polyline_segments; it refines on the object's own
+    // theta and throws where the object has no orientation state)
+    int fitSegments(const Mat1f& response, const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags, float epsilon,
+                    std::vector<std::vector<float> >& lines, std::vector<std::vector<float> >* rms = 0);
 
 protected:
     // the reference's protected members, same names (SteerableFiltersG4.h:50-56): 11 tap vectors; the planes m_g4a..m_h4f

@@ -529,6 +529,72 @@ int cvs_chain_measures(cvs_handle h, const int32_t* points, int n_points,
                        const float* strength,  /* NULL: peak_index -1, peak -INF, weakest +INF, sum 0 */
                        cvs_chain_measure* table, int mem);
 
+/* EXTENSION: contour segments -- table[k] is the total-least-squares line through the points of the polyline span that starts at vertex k
+ * of a cvs_chain_polylines result, fitted to the sub-pixel positions of cvs_chain_refine (or to the integer points), weighted by their
+ * strengths (or not).  One record per vertex, so the table lines up with `index`: no count, no prefix sum, nothing read back.  Needs no
+ * image size (any handle, before or after a setup).
+ * SPANS.  Vertex k belongs to polyline c = the largest c with polylines[c].start <= k (the rule of `ranges` in cvs_chain_refine_batch: an
+ * entry of length 0 is skipped).  With (S, L, F) = chains[c] and (vs, vl) = polylines[c]: if k + 1 < vs + vl the span is the points at
+ * positions index[k] .. index[k+1], both ends included (a vertex belongs to both of its spans); if k is the polyline's last vertex and
+ * F has CVS_CHAIN_CLOSED it is the positions index[k] .. S+L-1 followed by S .. index[vs], flag CVS_SEG_WRAPS (a closed chain with one
+ * vertex: the whole cycle, L + 1 points); otherwise -- the last vertex of an open polyline -- there is no span.  first = index[k], count =
+ * the number of points of the span (>= 2) or 0, chain = c.  A record without a span has first, count = 0, chain, and every other word 0.
+ * TERMS.  (x0, y0) = points[first] widened to double.  Per point i of the span dx = (double)xs_i - x0, dy = (double)ys_i - y0 with
+ * (xs, ys) from xy when it is given, else the integer point (both differences are exact for |coordinates| < 2^28); the weight wi is 1 when
+ * strength == NULL, else (double)strength_i if strength_i > 0 (false for NaN), else 0.  The terms, every operation rounded on its own:
+ * wi, wi*dx, wi*dy, (wi*dx)*dx, (wi*dx)*dy, (wi*dy)*dy; w, sx, sy, sxx, sxy, syy are their IEEE double sums in an order fixed by `count`
+ * alone (the rule of cvs_chain_measures: a lane adds every 16th term in ascending order where count <= 256, every 256th otherwise, and the
+ * lanes are combined by a butterfly): the same call twice gives the same bytes.  No floating-point atomic is used.  The moments are stored so that a caller who merges collinear
+ * spans can shift them by the integer offset of the two `first` pixels and add them.
+ * LINE.  From the six sums, in double, exactly this sequence (no contraction; division and sqrt correctly rounded):
+ *   mx = sx/w; my = sy/w;  a = sxx - sx*mx; b = sxy - sx*my; c = syy - sy*my;  d = a - c; e = b + b; r = sqrt(d*d + e*e);
+ *   (vx, vy) = d >= 0 ? (d + r, e) : (e, r - d)   -- the eigenvector of the larger eigenvalue, in the form that does not cancel;
+ *   hh = sqrt(vx*vx + vy*vy); ux = vx/hh; uy = vy/hh;
+ *   q = the last point's (dx, dy) minus the first point's, s = ux*qx + uy*qy; (ux, uy) is negated if s < 0, or if s == 0 and (ux < 0, or
+ *   ux == 0 and uy < 0): the direction runs from the first point towards the last;
+ *   cx = x0 + mx; cy = y0 + my;  t0 = ux*(dx_first - mx) + uy*(dy_first - my), t1 the same for the last point: the segment is
+ *   (cx, cy) + t * (ux, uy), t in [t0, t1];
+ *   lmin = 0.5*((a + c) - r), replaced by 0 unless it is > 0; rms = sqrt(lmin / w): the weighted RMS distance of the points from the line;
+ *   dmax = the largest |ux*(dy_i - my) - uy*(dx_i - mx)| over ALL points of the span, whatever their weight (a second pass; a maximum does
+ *   not depend on the order).
+ * If !(w > 0), !(hh > 0) or hh is infinite -- a NaN anywhere in the span's xy, all weights 0, all points equal -- the flag
+ * CVS_SEG_DEGENERATE is set, ux, uy, t0, t1, rms and dmax are NaN, cx and cy are as computed (NaN when w is not > 0), the sums are stored
+ * as they came out, and the second pass is skipped.
+ * points, chains, polylines, index, xy, strength and table are all in host or all in device memory (mem).  Device arrays: two launches --
+ * sixteen lanes per span of up to 256 points, one 256-lane workgroup per longer span -- queued on the handle's stream, nothing read back,
+ * capturable; the launch sequence depends on n_vertices alone.  Host arrays are staged in handle scratch (grown only, freed by
+ * cvs_destroy), the call synchronises, and it returns CVS_E_UNSUPPORTED while the stream is being captured.  n_vertices == 0: CVS_OK,
+ * nothing queued.
+ * CVS_E_BADARG, nothing written: a negative count; a required array missing (points with n_points > 0, chains / polylines with
+ * n_chains > 0, index / table with n_vertices > 0); n_vertices > 0 with n_chains == 0; an invalid mem; a pointer not aligned to 4 bytes, or
+ * to 8 for table; a table that overlaps an input; and, for HOST arrays, a chains entry that violates start >= 0, length >= 1,
+ * start + length <= n_points, polylines whose starts are not the running sum of their lengths from 0 to n_vertices, an index that is not
+ * strictly increasing inside each polyline or that leaves its chain's [S, S+L).  n_points > 2^30: CVS_E_SIZE.
+ * DEVICE tables are trusted for their meaning only: the binary search cannot leave 0 .. n_chains - 1; a vertex whose chain entry fails
+ * the three conditions, whose index[k], index[k+1] or index[vs] lies outside [S, S+L), whose index[k] >= index[k+1], or that does not lie
+ * inside the polyline the search found, gets the record without a span -- so no load leaves the arrays; coordinates are never used as
+ * addresses.  A table of cvs_contour_chains_batch goes through as it is: its starts are global, and `reserved` is not read. */
+typedef struct cvs_segment {          /* 128 bytes */
+    int32_t first;                    /* index[k]: position in `points` of the span's first point */
+    int32_t count;                    /* points of the span, >= 2; 0: no span */
+    int32_t chain;                    /* the polyline (= chain) the vertex belongs to */
+    int32_t flags;                    /* CVS_SEG_WRAPS = 1, CVS_SEG_DEGENERATE = 2 */
+    double  w, sx, sy, sxx, sxy, syy; /* weighted moments about the span's first pixel */
+    double  cx, cy;                   /* the weighted centroid: a point of the line */
+    double  ux, uy;                   /* unit direction, from the first point towards the last */
+    double  t0, t1;                   /* the first and the last point projected on the line: (cx, cy) + t * (ux, uy) */
+    double  rms, dmax;                /* weighted RMS and largest distance of the span's points from the line */
+} cvs_segment;
+enum { CVS_SEG_WRAPS = 1, CVS_SEG_DEGENERATE = 2 };
+int cvs_polyline_segments(cvs_handle h,
+        const int32_t* points, int n_points,
+        const cvs_chain* chains, const cvs_chain* polylines, int n_chains,
+        const int32_t* index, int n_vertices,
+        const float* xy,        /* NULL: fit the integer points */
+        const float* strength,  /* NULL: unit weights */
+        cvs_segment* table,     /* n_vertices records */
+        int mem);
+
 /* ---- EXTENSION beyond the reference: the contour chain on the batch axis -- cvs_link, cvs_nonmax_batch, cvs_contours_batch ----
  * None of the three reads anything back: with device planes they queue a launch sequence that depends on the image size, the number of
  * planes and how the planes lie in memory (one constant stride, or not) -- never on what the planes hold -- and return. */
