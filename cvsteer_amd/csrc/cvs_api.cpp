@@ -104,6 +104,7 @@ int cvs::do_setup(cvs_handle h, const SetupReq& rq)
     const bool fresh = h->last_image != (const void*)image->data && !rq.pipe_outs;
     h->last_image = image->data;
     a.strip_rows = default_strip_rows(h, a.rows, a.cols, fresh);
+    a.block_order = h->block_order >= 0 ? h->block_order : 0;   // the default's order (default_config): what basis_u8_fusable below judges
     // New images of 24 MiB and more: the waves of the launch's first fifth of row bands also touch the rest of the image (four
     // bands each), so that it is requested from HBM while the launch is young and most of the launch streams its writes without
     // reads mixed in.  Same process, alternating settings (profiles/r05_fresh_warm.txt): basis pass on alternating 8192^2 images

@@ -7,13 +7,13 @@
 
 #include <vector>
 
+#include "cvs_grid.h"   // kOrderXcdColumns, kOrderDynamic and every grid that follows the image height
+
 namespace cvs {
 
 constexpr int kMaxWidth = 32;           // generic path: up to 65 taps
 constexpr int kMaxTaps = 2 * kMaxWidth + 1;
 constexpr int kMaxBasis = 11;
-constexpr int kOrderXcdColumns = 1000000;  // BasisArgs::block_order: every XCD owns a contiguous range of column blocks
-constexpr int kOrderDynamic = 2000000;     // BasisArgs::block_order: the tail of the launch is taken from per-XCD queues (tile_ctr)
 
 struct PlaneRef {
     float* p;       // nullptr = not requested

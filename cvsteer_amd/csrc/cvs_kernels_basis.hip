@@ -1225,12 +1225,13 @@ __global__ __launch_bounds__(256) void k_rowpass_generic(const float* in, size_t
                                                           float* out, size_t out_pitch, TapVec kx, int w)
 {
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
-    const int y = blockIdx.y;
-    if (x >= cols || y >= rows) return;
-    const float* rp = in + (size_t)y * in_pitch;
-    float acc = kx.k[0] * rp[reflect101(x - w, cols)];
-    for (int i = 1; i <= 2 * w; ++i) acc = fmaf(kx.k[i], rp[reflect101(x - w + i, cols)], acc);
-    out[(size_t)y * out_pitch + x] = acc;
+    if (x >= cols) return;
+    for (int y = blockIdx.y; y < rows; y += gridDim.y) {   // (generic_grid: one workgroup row per image row up to kGridMaxYZ)
+        const float* rp = in + (size_t)y * in_pitch;
+        float acc = kx.k[0] * rp[reflect101(x - w, cols)];
+        for (int i = 1; i <= 2 * w; ++i) acc = fmaf(kx.k[i], rp[reflect101(x - w + i, cols)], acc);
+        out[(size_t)y * out_pitch + x] = acc;
+    }
 }
 
 // sym = +1 / -1: the column kernel is a mirror / anti-mirror image of itself and the CPU reference takes its folded column
@@ -1240,20 +1241,21 @@ __global__ __launch_bounds__(256) void k_colpass_generic(const float* in, size_t
                                                           float* out, size_t out_pitch, TapVec ky, int w, int sym)
 {
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
-    const int y = blockIdx.y;
-    if (x >= cols || y >= rows) return;
-    float acc;
-    if (sym != 0) {
-        acc = sym > 0 ? ky.k[w] * in[(size_t)y * in_pitch + x] : 0.0f;
-        for (int j = 1; j <= w; ++j) {
-            const float hi = in[(size_t)reflect101(y + j, rows) * in_pitch + x], lo = in[(size_t)reflect101(y - j, rows) * in_pitch + x];
-            acc = fmaf(ky.k[w + j], sym > 0 ? hi + lo : hi - lo, acc);
+    if (x >= cols) return;
+    for (int y = blockIdx.y; y < rows; y += gridDim.y) {
+        float acc;
+        if (sym != 0) {
+            acc = sym > 0 ? ky.k[w] * in[(size_t)y * in_pitch + x] : 0.0f;
+            for (int j = 1; j <= w; ++j) {
+                const float hi = in[(size_t)reflect101(y + j, rows) * in_pitch + x], lo = in[(size_t)reflect101(y - j, rows) * in_pitch + x];
+                acc = fmaf(ky.k[w + j], sym > 0 ? hi + lo : hi - lo, acc);
+            }
+        } else {
+            acc = ky.k[0] * in[(size_t)reflect101(y - w, rows) * in_pitch + x];
+            for (int j = 1; j <= 2 * w; ++j) acc = fmaf(ky.k[j], in[(size_t)reflect101(y - w + j, rows) * in_pitch + x], acc);
         }
-    } else {
-        acc = ky.k[0] * in[(size_t)reflect101(y - w, rows) * in_pitch + x];
-        for (int j = 1; j <= 2 * w; ++j) acc = fmaf(ky.k[j], in[(size_t)reflect101(y - w + j, rows) * in_pitch + x], acc);
+        out[(size_t)y * out_pitch + x] = acc;
     }
-    out[(size_t)y * out_pitch + x] = acc;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1314,19 +1316,6 @@ bool basis_may_need_scratch(int kind, int width, const float (*taps)[kMaxTaps], 
     if (rows < 3 * width + 1 || cols < width + 1) return true;
     // huge planes go through the fast kernel in row bands unless not even one strip fits 2 GiB (see band_rows)
     return kMaxPlaneBytes / (max_pitch * sizeof(float)) < (size_t)(2 * width + 2);
-}
-
-// dynamic order: the last tenth of the tiles goes through the queues (the rest: tile = workgroup index) with a quarter more
-// workgroups than queued tiles (see pick_tile; both figures from the sweep in profiles/r04_order_probe.txt), a multiple of 8 so
-// that every XCD gets the same number
-static unsigned dynamic_blocks(size_t ntiles, int* dyn_static)
-{
-    constexpr int pct = 25, tail_pct = 10;
-    const size_t tail = std::max<size_t>(8, ntiles * tail_pct / 100);
-    const size_t stat = ntiles > tail ? (ntiles - tail) / 8 * 8 : 0;
-    *dyn_static = (int)stat;
-    const size_t queued = ntiles - stat;
-    return (unsigned)(stat + (queued + queued * pct / 100 + 7) / 8 * 8);
 }
 
 // one set of queues back to zero, with the same agent-scope stores the strip kernels use on them.  (NOT hipMemsetAsync: a memset
@@ -1394,6 +1383,12 @@ struct StripPlan {
 // The plan of one strip launch, from its arguments after banding: the grid and the variant choices, and the launcher's fields of `a`
 // (grid_x, grid_y, dyn_nz, dyn_static, warm_bands, the final warm_k, z_ways, the normalised block_order).  `bank`: the folded taps of a
 // single-bank launch (the G2 bank: k_basis, k_basis_lit); nullptr = the G4 pair launch (k_basis_pair).
+static int strip_order(const BasisArgs& a)   // the order a strip launch of `a` runs in
+{
+    if (a.block_order == kOrderDynamic) return a.tile_ctr ? kOrderDynamic : 0;   // no queue slot for this handle: the plain order
+    return a.block_order == kOrderXcdColumns ? kOrderXcdColumns : 0;
+}
+
 static StripPlan plan_strips(BasisArgs& a, const Folded<BankG2>* bank)
 {
     using B = BankG2;
@@ -1401,15 +1396,13 @@ static StripPlan plan_strips(BasisArgs& a, const Folded<BankG2>* bank)
     const bool pair = bank == nullptr;
     StripPlan p{};
     p.block = dim3(64 * wpb);
-    const int strips_x = (a.cols + 63) / 64;
-    a.grid_x = (strips_x + wpb - 1) / wpb;
-    a.grid_y = (a.row_hi - a.row_lo + a.strip_rows - 1) / a.strip_rows;
+    a.grid_x = strip_grid_x(a.cols);
+    a.grid_y = strip_grid_y(a.row_lo, a.row_hi, a.strip_rows);
     a.warm_bands = a.warm_k > 0 ? (a.grid_y + a.warm_k) / (a.warm_k + 1) : 0;
     // no read-ahead under ten bands; the single-bank launch none for table batches either (frame batches: warm_k is set by the API
     // layer only where it pays)
     if (a.grid_y < 10 || (!pair && a.frames)) a.warm_k = 0;
-    if (a.block_order == kOrderDynamic && !a.tile_ctr) a.block_order = 0;   // no queue slot for this handle: the plain order
-    if (a.block_order != kOrderDynamic && a.block_order != kOrderXcdColumns) a.block_order = 0;
+    a.block_order = strip_order(a);
     // planes of tiles (grid.z): the pair launch's two half banks, or a batch's frames -- dealt from z_ways parts, the grid a
     // multiple of z_ways (slots past the batch leave at once: pick_frame_tile)
     unsigned nz = 1;
@@ -1420,12 +1413,9 @@ static StripPlan plan_strips(BasisArgs& a, const Folded<BankG2>* bank)
         nz = (unsigned)((a.batch + a.z_ways - 1) / a.z_ways * a.z_ways);
     }
     a.dyn_nz = (int)nz;
-    if (a.block_order == kOrderDynamic)   // one row of workgroups over all z-planes; pick_tile deals the tiles
-        p.grid = dim3(dynamic_blocks((size_t)a.grid_x * a.grid_y * nz, &a.dyn_static));
-    else if (a.block_order == kOrderXcdColumns)
-        p.grid = dim3(8u * (unsigned)(((a.grid_x + 7) / 8) * a.grid_y), 1, nz);
-    else
-        p.grid = dim3(a.grid_x, a.grid_y, nz);
+    // (dynamic order: one row of workgroups over all z-planes; pick_tile deals the tiles)
+    const GridDims g = strip_grid(a.block_order, a.grid_x, a.grid_y, nz, &a.dyn_static);
+    p.grid = dim3(g.x, g.y, g.z);
     // the single-resource form addresses the whole image from row 0: a banded launch (a caller plane of 2 GiB or
     // more beside a small state block, e.g. a narrow column view of a huge image) must use the per-plane form,
     // which honours row_lo / row_hi / row_base
@@ -1564,7 +1554,8 @@ static hipError_t launch_generic(int kind, int width, const float (*taps)[kMaxTa
                                  float* scratch, hipStream_t s)
 {
     const int nb = host_num_basis(kind);
-    dim3 block(256), grid((a.cols + 255) / 256, a.rows);
+    const GridDims gd = generic_grid(a.rows, a.cols);
+    const dim3 block(256), grid(gd.x, gd.y, gd.z);
     const size_t spitch = ((size_t)a.cols + 63) / 64 * 64;   // the scratch plane is dense whatever the layout of the state planes
     for (int p = 0; p < nb; ++p) {
         int ix, iy;
@@ -1637,11 +1628,10 @@ static bool fast_geometry_ok(const BasisArgs& a, int width)
 // 0 = a single strip does not fit (rows of ~100 MiB and more): generic path.
 static int band_rows(const BasisArgs& a, int width)
 {
-    const size_t fit = kMaxPlaneBytes / max_pitch_bytes(a);
-    if (fit >= (size_t)a.rows) return a.rows;
-    if (fit < (size_t)(2 * width + 2)) return 0;
-    const int room = (int)fit - 2 * width;
-    return room >= a.strip_rows ? room / a.strip_rows * a.strip_rows : room;  // very wide rows: one short strip per band
+    // ... and so that the launch's grid stays inside the bounds of cvs_grid.h (a tall image in the plain order: at most kGridMaxYZ
+    // strips per launch; the one-dimensional orders: strip_band_cap).  The G4 pair launch has two planes of tiles.
+    const long long cap = strip_band_cap(strip_order(a), strip_grid_x(a.cols), a.strip_rows > 0 ? a.strip_rows : 1, a.basis2 ? 2u : 1u);
+    return strip_band_rows(a.rows, kMaxPlaneBytes / max_pitch_bytes(a), width, a.strip_rows, cap);
 }
 
 // true when launch_basis can emit the next pyramid level from inside the filter launch (a.pyr_out): the G2 bank at its
@@ -1676,6 +1666,7 @@ bool launch_pyr_strip(const float* src, size_t spitch, int rows, int cols, float
     a.row_lo = 0;
     a.row_hi = rows;
     a.row_base = 0;
+    if (strip_band_cap(0, strip_grid_x(cols), a.strip_rows, 1u) < rows) return false;   // more strips than one plain grid holds: k_pyr_down strides
     // the march's plan: its own 46-row strips, the plain order (block_order 0, no queues), plain stores, no state block (not ONE), no LDS pad
     Folded<BankG2> f{};
     const StripPlan p = plan_strips(a, &f);

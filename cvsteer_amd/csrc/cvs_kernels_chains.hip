@@ -38,26 +38,29 @@ __global__ __launch_bounds__(256) void k_ch_links(const MaskRef mask, int rows, 
 {
     const int lane = threadIdx.x & 63;
     const int x = blockIdx.x * 256 + threadIdx.x;
-    const int y0 = blockIdx.y * kChRows, y1 = y0 + kChRows < rows ? y0 + kChRows : rows;
     const int xe = lane == 0 ? x - 1 : (lane == 63 ? x + 1 : -1);
-    // bit 0: row y - 1, bit 1: row y, bit 2: row y + 1 (after the shift at the top of the loop)
-    unsigned own = (ch_fg(mask, rows, cols, y0 - 1, x) ? 2u : 0u) | (ch_fg(mask, rows, cols, y0, x) ? 4u : 0u);
-    unsigned ext = (ch_fg(mask, rows, cols, y0 - 1, xe) ? 2u : 0u) | (ch_fg(mask, rows, cols, y0, xe) ? 4u : 0u);
-    for (int y = y0; y < y1; ++y) {
-        own = (own >> 1) | (ch_fg(mask, rows, cols, y + 1, x) ? 4u : 0u);
-        ext = (ext >> 1) | (ch_fg(mask, rows, cols, y + 1, xe) ? 4u : 0u);
-        unsigned l = __shfl_up(own, 1, 64), r = __shfl_down(own, 1, 64);
-        if (lane == 0) l = ext;
-        if (lane == 63) r = ext;
-        if (x >= cols) continue;
-        unsigned v = 0;
-        if (own & 2u) {
-            const unsigned n = own & 1u, s = (own >> 2) & 1u, w = (l >> 1) & 1u, e = (r >> 1) & 1u;
-            const unsigned nw = l & 1u & ~(n | w), ne = r & 1u & ~(n | e), sw = (l >> 2) & 1u & ~(s | w), se = (r >> 2) & 1u & ~(s | e);
-            v = nw | (n << 1) | (ne << 2) | (w << 3) | (e << 4) | (sw << 5) | (s << 6) | (se << 7);
-            v |= kChFg | (__popc(v) != 2 ? kChNode : 0u);
+    const int bands = tile_row_count(rows, kChRows);   // tile_grid deals the 32-row bands over at most kGridMaxYZ workgroup rows
+    for (int by = blockIdx.y; by < bands; by += gridDim.y) {
+        const int y0 = by * kChRows, y1 = y0 + kChRows < rows ? y0 + kChRows : rows;
+        // bit 0: row y - 1, bit 1: row y, bit 2: row y + 1 (after the shift at the top of the loop)
+        unsigned own = (ch_fg(mask, rows, cols, y0 - 1, x) ? 2u : 0u) | (ch_fg(mask, rows, cols, y0, x) ? 4u : 0u);
+        unsigned ext = (ch_fg(mask, rows, cols, y0 - 1, xe) ? 2u : 0u) | (ch_fg(mask, rows, cols, y0, xe) ? 4u : 0u);
+        for (int y = y0; y < y1; ++y) {
+            own = (own >> 1) | (ch_fg(mask, rows, cols, y + 1, x) ? 4u : 0u);
+            ext = (ext >> 1) | (ch_fg(mask, rows, cols, y + 1, xe) ? 4u : 0u);
+            unsigned l = __shfl_up(own, 1, 64), r = __shfl_down(own, 1, 64);
+            if (lane == 0) l = ext;
+            if (lane == 63) r = ext;
+            if (x >= cols) continue;
+            unsigned v = 0;
+            if (own & 2u) {
+                const unsigned n = own & 1u, s = (own >> 2) & 1u, w = (l >> 1) & 1u, e = (r >> 1) & 1u;
+                const unsigned nw = l & 1u & ~(n | w), ne = r & 1u & ~(n | e), sw = (l >> 2) & 1u & ~(s | w), se = (r >> 2) & 1u & ~(s | e);
+                v = nw | (n << 1) | (ne << 2) | (w << 3) | (e << 4) | (sw << 5) | (s << 6) | (se << 7);
+                v |= kChFg | (__popc(v) != 2 ? kChNode : 0u);
+            }
+            link[(size_t)y * cols + x] = (uint16_t)v;
         }
-        link[(size_t)y * cols + x] = (uint16_t)v;
     }
 }
 
@@ -378,8 +381,8 @@ static unsigned blocks_of(long long n, int per) { return (unsigned)((n + per - 1
 hipError_t launch_ch_links(const MaskRef& mask, int rows, int cols, uint16_t* link, hipStream_t s)
 {
     if (!size_ok(rows, cols) || !mask.p || !link) return hipErrorInvalidValue;
-    const dim3 grid((cols + 255) / 256, (rows + kChRows - 1) / kChRows);
-    hipLaunchKernelGGL(k_ch_links, grid, dim3(256), 0, s, mask, rows, cols, link);
+    const GridDims gd = tile_grid(rows, cols, 256, kChRows, 1);
+    hipLaunchKernelGGL(k_ch_links, dim3(gd.x, gd.y, gd.z), dim3(256), 0, s, mask, rows, cols, link);
     return hipGetLastError();
 }
 

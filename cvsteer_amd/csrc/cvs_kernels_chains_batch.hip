@@ -61,26 +61,29 @@ __global__ __launch_bounds__(256) void k_chb_links(const ChbArgs a)
     uint16_t* link = a.link + (size_t)z * rows * cols;
     const int lane = threadIdx.x & 63;
     const int x = blockIdx.x * 256 + threadIdx.x;
-    const int y0 = blockIdx.y * kChbRows, y1 = y0 + kChbRows < rows ? y0 + kChbRows : rows;
     const int xe = lane == 0 ? x - 1 : (lane == 63 ? x + 1 : -1);
-    // bit 0: row y - 1, bit 1: row y, bit 2: row y + 1 (after the shift at the top of the loop)
-    unsigned own = (chb_fg(mask, rows, cols, y0 - 1, x) ? 2u : 0u) | (chb_fg(mask, rows, cols, y0, x) ? 4u : 0u);
-    unsigned ext = (chb_fg(mask, rows, cols, y0 - 1, xe) ? 2u : 0u) | (chb_fg(mask, rows, cols, y0, xe) ? 4u : 0u);
-    for (int y = y0; y < y1; ++y) {
-        own = (own >> 1) | (chb_fg(mask, rows, cols, y + 1, x) ? 4u : 0u);
-        ext = (ext >> 1) | (chb_fg(mask, rows, cols, y + 1, xe) ? 4u : 0u);
-        unsigned l = __shfl_up(own, 1, 64), r = __shfl_down(own, 1, 64);
-        if (lane == 0) l = ext;
-        if (lane == 63) r = ext;
-        if (x >= cols) continue;
-        unsigned v = 0;
-        if (own & 2u) {
-            const unsigned n = own & 1u, s = (own >> 2) & 1u, w = (l >> 1) & 1u, e = (r >> 1) & 1u;
-            const unsigned nw = l & 1u & ~(n | w), ne = r & 1u & ~(n | e), sw = (l >> 2) & 1u & ~(s | w), se = (r >> 2) & 1u & ~(s | e);
-            v = nw | (n << 1) | (ne << 2) | (w << 3) | (e << 4) | (sw << 5) | (s << 6) | (se << 7);
-            v |= kChFg | (__popc(v) != 2 ? kChNode : 0u);
+    const int bands = tile_row_count(rows, kChbRows);   // tile_grid deals the 32-row bands over at most kGridMaxYZ workgroup rows
+    for (int by = blockIdx.y; by < bands; by += gridDim.y) {
+        const int y0 = by * kChbRows, y1 = y0 + kChbRows < rows ? y0 + kChbRows : rows;
+        // bit 0: row y - 1, bit 1: row y, bit 2: row y + 1 (after the shift at the top of the loop)
+        unsigned own = (chb_fg(mask, rows, cols, y0 - 1, x) ? 2u : 0u) | (chb_fg(mask, rows, cols, y0, x) ? 4u : 0u);
+        unsigned ext = (chb_fg(mask, rows, cols, y0 - 1, xe) ? 2u : 0u) | (chb_fg(mask, rows, cols, y0, xe) ? 4u : 0u);
+        for (int y = y0; y < y1; ++y) {
+            own = (own >> 1) | (chb_fg(mask, rows, cols, y + 1, x) ? 4u : 0u);
+            ext = (ext >> 1) | (chb_fg(mask, rows, cols, y + 1, xe) ? 4u : 0u);
+            unsigned l = __shfl_up(own, 1, 64), r = __shfl_down(own, 1, 64);
+            if (lane == 0) l = ext;
+            if (lane == 63) r = ext;
+            if (x >= cols) continue;
+            unsigned v = 0;
+            if (own & 2u) {
+                const unsigned n = own & 1u, s = (own >> 2) & 1u, w = (l >> 1) & 1u, e = (r >> 1) & 1u;
+                const unsigned nw = l & 1u & ~(n | w), ne = r & 1u & ~(n | e), sw = (l >> 2) & 1u & ~(s | w), se = (r >> 2) & 1u & ~(s | e);
+                v = nw | (n << 1) | (ne << 2) | (w << 3) | (e << 4) | (sw << 5) | (s << 6) | (se << 7);
+                v |= kChFg | (__popc(v) != 2 ? kChNode : 0u);
+            }
+            link[(size_t)y * cols + x] = (uint16_t)v;
         }
-        link[(size_t)y * cols + x] = (uint16_t)v;
     }
 }
 
@@ -94,56 +97,60 @@ __global__ __launch_bounds__(256) void k_chb_tiles(const ChbArgs a)
     __shared__ int L[kBH * kBW];
     const int z = a.z0 + blockIdx.z, rows = a.rows, cols = a.cols;
     const MaskRef mask = plane_of(a.masks, z);
-    const int x0 = blockIdx.x * kBW, y0 = blockIdx.y * kBH;
-    const int tx = threadIdx.x & (kBW - 1), half = threadIdx.x >> 7, lane = threadIdx.x & 63;
-    const int x = x0 + tx;
-    unsigned fgbits = 0;
+    const int nty = tile_row_count(rows, kBH);   // tile_grid deals the tile rows over at most kGridMaxYZ workgroup rows
+    for (int by = blockIdx.y; by < nty; by += gridDim.y) {
+        if (by != (int)blockIdx.y) __syncthreads();   // the previous tile's lookups are done before L is written again
+        const int x0 = blockIdx.x * kBW, y0 = by * kBH;
+        const int tx = threadIdx.x & (kBW - 1), half = threadIdx.x >> 7, lane = threadIdx.x & 63;
+        const int x = x0 + tx;
+        unsigned fgbits = 0;
 #pragma unroll
-    for (int k = 0; k < kBH / 2; ++k) {
-        const int ty = 2 * k + half, y = y0 + ty;
-        const bool fg = chb_fg(mask, rows, cols, y, x);
-        const unsigned long long gaps = ~__ballot(fg) & ((1ull << lane) - 1ull);   // background lanes left of this one
-        const int start = gaps ? 64 - __clzll((long long)gaps) : 0;                 // first lane of this pixel's run
-        const int i = ty * kBW + tx;
-        L[i] = fg ? i - lane + start : -1;
-        fgbits |= (fg ? 1u : 0u) << k;
-    }
-    __syncthreads();
+        for (int k = 0; k < kBH / 2; ++k) {
+            const int ty = 2 * k + half, y = y0 + ty;
+            const bool fg = chb_fg(mask, rows, cols, y, x);
+            const unsigned long long gaps = ~__ballot(fg) & ((1ull << lane) - 1ull);   // background lanes left of this one
+            const int start = gaps ? 64 - __clzll((long long)gaps) : 0;                 // first lane of this pixel's run
+            const int i = ty * kBW + tx;
+            L[i] = fg ? i - lane + start : -1;
+            fgbits |= (fg ? 1u : 0u) << k;
+        }
+        __syncthreads();
 #pragma unroll 1
-    for (int k = 0; k < kBH / 2; ++k) {
-        if (!((fgbits >> k) & 1u)) continue;
-        const int ty = 2 * k + half, i = ty * kBW + tx;
-        const bool up = ty > 0;
-        const bool n = up && lds_get(L, i - kBW) >= 0;
-        const bool nw = up && tx > 0 && lds_get(L, i - kBW - 1) >= 0;
-        const bool ne = up && tx < kBW - 1 && lds_get(L, i - kBW + 1) >= 0;
-        const bool in_run = lane > 0 && lds_get(L, i - 1) >= 0;   // the left neighbour is in this pixel's run (same initial parent)
-        if (!in_run) {
-            if (tx == 64 && lds_get(L, i - 1) >= 0) lds_union(L, i, i - 1);   // the run goes on in the other wave's half of the row
-            if (n) {
-                lds_union(L, i, i - kBW);   // (nw and ne touch n in their own row)
-            } else {
-                if (nw) lds_union(L, i, i - kBW - 1);
-                if (ne) lds_union(L, i, i - kBW + 1);
+        for (int k = 0; k < kBH / 2; ++k) {
+            if (!((fgbits >> k) & 1u)) continue;
+            const int ty = 2 * k + half, i = ty * kBW + tx;
+            const bool up = ty > 0;
+            const bool n = up && lds_get(L, i - kBW) >= 0;
+            const bool nw = up && tx > 0 && lds_get(L, i - kBW - 1) >= 0;
+            const bool ne = up && tx < kBW - 1 && lds_get(L, i - kBW + 1) >= 0;
+            const bool in_run = lane > 0 && lds_get(L, i - 1) >= 0;   // the left neighbour is in this pixel's run (same initial parent)
+            if (!in_run) {
+                if (tx == 64 && lds_get(L, i - 1) >= 0) lds_union(L, i, i - 1);   // the run goes on in the other wave's half of the row
+                if (n) {
+                    lds_union(L, i, i - kBW);   // (nw and ne touch n in their own row)
+                } else {
+                    if (nw) lds_union(L, i, i - kBW - 1);
+                    if (ne) lds_union(L, i, i - kBW + 1);
+                }
+            } else if (!n && ne) {
+                lds_union(L, i, i - kBW + 1);   // every other contact of a pixel inside a run is made by its left neighbour
             }
-        } else if (!n && ne) {
-            lds_union(L, i, i - kBW + 1);   // every other contact of a pixel inside a run is made by its left neighbour
         }
-    }
-    __syncthreads();
-    const int zbase = z * rows * cols;   // (n * rows * cols <= 2^28)
+        __syncthreads();
+        const int zbase = z * rows * cols;   // (n * rows * cols <= 2^28)
 #pragma unroll 1
-    for (int k = 0; k < kBH / 2; ++k) {
-        const int ty = 2 * k + half, y = y0 + ty;
-        if (y >= rows || x >= cols) continue;
-        int v = -1;
-        if ((fgbits >> k) & 1u) {
-            const int r = lds_find(L, ty * kBW + tx);
-            v = zbase + (y0 + r / kBW) * cols + x0 + r % kBW;
+        for (int k = 0; k < kBH / 2; ++k) {
+            const int ty = 2 * k + half, y = y0 + ty;
+            if (y >= rows || x >= cols) continue;
+            int v = -1;
+            if ((fgbits >> k) & 1u) {
+                const int r = lds_find(L, ty * kBW + tx);
+                v = zbase + (y0 + r / kBW) * cols + x0 + r % kBW;
+            }
+            const size_t g = (size_t)zbase + (size_t)y * cols + x;
+            a.parent[g] = v;
+            a.aux[g] = 0;
         }
-        const size_t g = (size_t)zbase + (size_t)y * cols + x;
-        a.parent[g] = v;
-        a.aux[g] = 0;
     }
 }
 
@@ -157,7 +164,7 @@ __global__ __launch_bounds__(256) void k_chb_borders(int rows, int cols, int z0,
 {
     const int zbase = (z0 + (int)blockIdx.z) * rows * cols;
     const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
-    const int nty = (rows + kBH - 1) / kBH, ntx = (cols + kBW - 1) / kBW;
+    const int nty = tile_row_count(rows, kBH), ntx = tile_row_count(cols, kBW);
     const long long n_top = (long long)(nty - 1) * cols, n_left = (long long)(ntx - 1) * rows;
     if (id < n_top) {   // (x, y) on the top row of tile row t >= 1: the three neighbours in row y - 1
         const int x = (int)(id % cols), y = (int)(id / cols + 1) * kBH;
@@ -408,7 +415,8 @@ hipError_t launch_chb_links(const ChbArgs& a, hipStream_t s)
     return each_slab(a.n, [&](int z0, int nz) {
         ChbArgs b = a;
         b.z0 = z0;
-        hipLaunchKernelGGL(k_chb_links, dim3((a.cols + 255) / 256, (a.rows + kChbRows - 1) / kChbRows, nz), dim3(256), 0, s, b);
+        const GridDims gd = tile_grid(a.rows, a.cols, 256, kChbRows, nz);
+        hipLaunchKernelGGL(k_chb_links, dim3(gd.x, gd.y, gd.z), dim3(256), 0, s, b);
     });
 }
 
@@ -418,14 +426,15 @@ hipError_t launch_chb_tiles(const ChbArgs& a, hipStream_t s)
     return each_slab(a.n, [&](int z0, int nz) {
         ChbArgs b = a;
         b.z0 = z0;
-        hipLaunchKernelGGL(k_chb_tiles, dim3((a.cols + kBW - 1) / kBW, (a.rows + kBH - 1) / kBH, nz), dim3(256), 0, s, b);
+        const GridDims gd = tile_grid(a.rows, a.cols, kBW, kBH, nz);
+        hipLaunchKernelGGL(k_chb_tiles, dim3(gd.x, gd.y, gd.z), dim3(256), 0, s, b);
     });
 }
 
 hipError_t launch_chb_borders(const ChbArgs& a, hipStream_t s)
 {
     if (!chb_ok(a)) return hipErrorInvalidValue;
-    const long long nty = (a.rows + kBH - 1) / kBH, ntx = (a.cols + kBW - 1) / kBW;
+    const long long nty = tile_row_count(a.rows, kBH), ntx = tile_row_count(a.cols, kBW);
     const long long lanes = (nty - 1) * a.cols + (ntx - 1) * a.rows;
     const long long blocks = lanes > 0 ? (lanes + 255) / 256 : 1;   // (a single tile: one workgroup that finds nothing to do)
     return each_slab(a.n, [&](int z0, int nz) {

@@ -36,56 +36,60 @@ __device__ __forceinline__ bool mask_fg(const MaskRef& m, int y, int x)
 __global__ __launch_bounds__(256) void k_cc_tiles(const MaskRef mask, int rows, int cols, int32_t* parent, int32_t* zero_a, uint32_t* zero_b)
 {
     __shared__ int L[kTH * kTW];
-    const int x0 = blockIdx.x * kTW, y0 = blockIdx.y * kTH;
-    const int tx = threadIdx.x & (kTW - 1), half = threadIdx.x >> 7, lane = threadIdx.x & 63;
-    const int x = x0 + tx;
-    unsigned fgbits = 0;
+    const int nty = tile_row_count(rows, kTH);   // tile_grid deals the tile rows over at most kGridMaxYZ workgroup rows
+    for (int by = blockIdx.y; by < nty; by += gridDim.y) {
+        if (by != (int)blockIdx.y) __syncthreads();   // the previous tile's lookups are done before L is written again
+        const int x0 = blockIdx.x * kTW, y0 = by * kTH;
+        const int tx = threadIdx.x & (kTW - 1), half = threadIdx.x >> 7, lane = threadIdx.x & 63;
+        const int x = x0 + tx;
+        unsigned fgbits = 0;
 #pragma unroll
-    for (int k = 0; k < kTH / 2; ++k) {
-        const int ty = 2 * k + half, y = y0 + ty;
-        const bool fg = y < rows && x < cols && mask_fg(mask, y, x);
-        const unsigned long long gaps = ~__ballot(fg) & ((1ull << lane) - 1ull);   // background lanes left of this one
-        const int start = gaps ? 64 - __clzll((long long)gaps) : 0;                 // first lane of this pixel's run
-        const int i = ty * kTW + tx;
-        L[i] = fg ? i - lane + start : -1;
-        fgbits |= (fg ? 1u : 0u) << k;
-    }
-    __syncthreads();
+        for (int k = 0; k < kTH / 2; ++k) {
+            const int ty = 2 * k + half, y = y0 + ty;
+            const bool fg = y < rows && x < cols && mask_fg(mask, y, x);
+            const unsigned long long gaps = ~__ballot(fg) & ((1ull << lane) - 1ull);   // background lanes left of this one
+            const int start = gaps ? 64 - __clzll((long long)gaps) : 0;                 // first lane of this pixel's run
+            const int i = ty * kTW + tx;
+            L[i] = fg ? i - lane + start : -1;
+            fgbits |= (fg ? 1u : 0u) << k;
+        }
+        __syncthreads();
 #pragma unroll 1
-    for (int k = 0; k < kTH / 2; ++k) {
-        if (!((fgbits >> k) & 1u)) continue;
-        const int ty = 2 * k + half, i = ty * kTW + tx;
-        const bool up = ty > 0;
-        const bool n = up && lds_get(L, i - kTW) >= 0;
-        const bool nw = up && tx > 0 && lds_get(L, i - kTW - 1) >= 0;
-        const bool ne = up && tx < kTW - 1 && lds_get(L, i - kTW + 1) >= 0;
-        const bool in_run = lane > 0 && lds_get(L, i - 1) >= 0;   // the left neighbour is in this pixel's run (same initial parent)
-        if (!in_run) {
-            if (tx == 64 && lds_get(L, i - 1) >= 0) lds_union(L, i, i - 1);   // the run goes on in the other wave's half of the row
-            if (n) {
-                lds_union(L, i, i - kTW);   // (nw and ne touch n in their own row)
-            } else {
-                if (nw) lds_union(L, i, i - kTW - 1);
-                if (ne) lds_union(L, i, i - kTW + 1);
+        for (int k = 0; k < kTH / 2; ++k) {
+            if (!((fgbits >> k) & 1u)) continue;
+            const int ty = 2 * k + half, i = ty * kTW + tx;
+            const bool up = ty > 0;
+            const bool n = up && lds_get(L, i - kTW) >= 0;
+            const bool nw = up && tx > 0 && lds_get(L, i - kTW - 1) >= 0;
+            const bool ne = up && tx < kTW - 1 && lds_get(L, i - kTW + 1) >= 0;
+            const bool in_run = lane > 0 && lds_get(L, i - 1) >= 0;   // the left neighbour is in this pixel's run (same initial parent)
+            if (!in_run) {
+                if (tx == 64 && lds_get(L, i - 1) >= 0) lds_union(L, i, i - 1);   // the run goes on in the other wave's half of the row
+                if (n) {
+                    lds_union(L, i, i - kTW);   // (nw and ne touch n in their own row)
+                } else {
+                    if (nw) lds_union(L, i, i - kTW - 1);
+                    if (ne) lds_union(L, i, i - kTW + 1);
+                }
+            } else if (!n && ne) {
+                lds_union(L, i, i - kTW + 1);   // every other contact of a pixel inside a run is made by its left neighbour
             }
-        } else if (!n && ne) {
-            lds_union(L, i, i - kTW + 1);   // every other contact of a pixel inside a run is made by its left neighbour
         }
-    }
-    __syncthreads();
+        __syncthreads();
 #pragma unroll 1
-    for (int k = 0; k < kTH / 2; ++k) {
-        const int ty = 2 * k + half, y = y0 + ty;
-        if (y >= rows || x >= cols) continue;
-        int v = -1;
-        if ((fgbits >> k) & 1u) {
-            const int r = lds_find(L, ty * kTW + tx);
-            v = (y0 + r / kTW) * cols + x0 + r % kTW;
+        for (int k = 0; k < kTH / 2; ++k) {
+            const int ty = 2 * k + half, y = y0 + ty;
+            if (y >= rows || x >= cols) continue;
+            int v = -1;
+            if ((fgbits >> k) & 1u) {
+                const int r = lds_find(L, ty * kTW + tx);
+                v = (y0 + r / kTW) * cols + x0 + r % kTW;
+            }
+            const size_t g = (size_t)y * cols + x;
+            parent[g] = v;
+            if (zero_a) zero_a[g] = 0;
+            if (zero_b) zero_b[g] = 0u;
         }
-        const size_t g = (size_t)y * cols + x;
-        parent[g] = v;
-        if (zero_a) zero_a[g] = 0;
-        if (zero_b) zero_b[g] = 0u;
     }
 }
 
@@ -100,7 +104,7 @@ __global__ __launch_bounds__(256) void k_cc_tiles(const MaskRef mask, int rows, 
 __global__ __launch_bounds__(256) void k_cc_borders(int rows, int cols, int32_t* parent)
 {
     const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
-    const int nty = (rows + kTH - 1) / kTH, ntx = (cols + kTW - 1) / kTW;
+    const int nty = tile_row_count(rows, kTH), ntx = tile_row_count(cols, kTW);
     const long long n_top = (long long)(nty - 1) * cols, n_left = (long long)(ntx - 1) * rows;
     if (id < n_top) {   // (x, y) on the top row of tile row t >= 1: the three neighbours in row y - 1
         const int x = (int)(id % cols), y = (int)(id / cols + 1) * kTH;
@@ -458,15 +462,15 @@ static dim3 row_grid(int rows, int cols)   // 256 columns per workgroup, rows de
 hipError_t launch_cc_tiles(const MaskRef& mask, int rows, int cols, int32_t* parent, int32_t* zero_a, uint32_t* zero_b, hipStream_t s)
 {
     if (!size_ok(rows, cols) || !mask.p || !parent) return hipErrorInvalidValue;
-    const dim3 grid((cols + kTW - 1) / kTW, (rows + kTH - 1) / kTH);
-    hipLaunchKernelGGL(k_cc_tiles, grid, dim3(256), 0, s, mask, rows, cols, parent, zero_a, zero_b);
+    const GridDims gd = tile_grid(rows, cols, kTW, kTH, 1);
+    hipLaunchKernelGGL(k_cc_tiles, dim3(gd.x, gd.y, gd.z), dim3(256), 0, s, mask, rows, cols, parent, zero_a, zero_b);
     return hipGetLastError();
 }
 
 hipError_t launch_cc_borders(int rows, int cols, int32_t* parent, hipStream_t s)
 {
     if (!size_ok(rows, cols) || !parent) return hipErrorInvalidValue;
-    const long long nty = (rows + kTH - 1) / kTH, ntx = (cols + kTW - 1) / kTW;
+    const long long nty = tile_row_count(rows, kTH), ntx = tile_row_count(cols, kTW);
     const long long lanes = (nty - 1) * cols + (ntx - 1) * rows;
     const long long blocks = lanes > 0 ? (lanes + 255) / 256 : 1;   // (a single tile: one workgroup that finds nothing to do)
     hipLaunchKernelGGL(k_cc_borders, dim3((unsigned)blocks), dim3(256), 0, s, rows, cols, parent);

@@ -19,7 +19,7 @@ namespace cvs {
 // strip (plus the halo rows above and below it), the next row's loads are in flight while the current row is decided, and theta is
 // read once for all NM maps.  Neighbours outside the image read as 0.0f.
 // ---------------------------------------------------------------------------------------
-constexpr int kNmsSpan = 62;   // output columns per wave
+constexpr int kNmsSpan = 62;   // output columns per wave (nonmax_grid in cvs_grid.h counts tiles of this width)
 
 struct Row3 {
     float l, c, r;   // columns x - 1, x, x + 1
@@ -137,16 +137,11 @@ static bool nonmax_ok(const NmsArgs& a)
     return true;
 }
 
-// rows per strip and the grid of one frame (the decisions do not depend on the strip: any strip gives the same values)
+// rows per strip and the grid of `frames` frames (cvs_grid.h: nonmax_grid)
 static dim3 nonmax_grid(NmsArgs& b, long frames)
 {
-    const long tiles = (b.cols + kNmsSpan - 1) / kNmsSpan;
-    // rows per strip: enough waves to keep every CU's memory pipeline busy (~8K waves), and at least 8 rows so that the two halo
-    // rows of a strip stay a small part of its reads
-    long strip = (long)b.rows * tiles * frames / 8192;
-    strip = strip < 8 ? 8 : strip > 64 ? 64 : strip;
-    b.strip = (int)strip;
-    return dim3((unsigned)((tiles + 3) / 4), (unsigned)((b.rows + strip - 1) / strip), (unsigned)frames);
+    const GridDims gd = nonmax_grid(b.rows, b.cols, frames, &b.strip);
+    return dim3(gd.x, gd.y, gd.z);
 }
 
 hipError_t launch_nonmax(const NmsArgs& a, hipStream_t s)
@@ -199,40 +194,44 @@ __global__ __launch_bounds__(256) void k_hyst_propagate(const HystArgs a, unsign
 {
     __shared__ unsigned char t[kHystTileH + 2][kHystTileW + 2];
     unsigned char* lab = a.lab + (size_t)blockIdx.z * a.lab_stride;
-    const int x0 = blockIdx.x * kHystTileW, y0 = blockIdx.y * kHystTileH;
-    for (int i = threadIdx.x; i < (kHystTileH + 2) * (kHystTileW + 2); i += blockDim.x) {
-        const int ty = i / (kHystTileW + 2), tx = i % (kHystTileW + 2);
-        const int y = y0 + ty - 1, x = x0 + tx - 1;
-        t[ty][tx] = (y >= 0 && y < a.rows && x >= 0 && x < a.cols) ? lab[(size_t)y * a.lab_pitch + x] : 0;
-    }
-    __syncthreads();
-    // lane -> one segment of one tile row, swept left to right and back, promoting in place: a run along the row is linked in one sweep
-    const int ty = 1 + threadIdx.x / 8, tx0 = 1 + (threadIdx.x % 8) * kHystSeg;
-    int any = 0;
-    for (;;) {
-        int ch = 0;
-        for (int dir = 0; dir < 2; ++dir)
-            for (int j = 0; j < kHystSeg; ++j) {
-                const int tx = dir ? tx0 + kHystSeg - 1 - j : tx0 + j;
-                if (t[ty][tx] != kWeak) continue;
-                const bool hit = t[ty - 1][tx - 1] == kStrong || t[ty - 1][tx] == kStrong || t[ty - 1][tx + 1] == kStrong ||
-                                 t[ty][tx - 1] == kStrong || t[ty][tx + 1] == kStrong || t[ty + 1][tx - 1] == kStrong ||
-                                 t[ty + 1][tx] == kStrong || t[ty + 1][tx + 1] == kStrong;
-                if (hit) {
-                    t[ty][tx] = kStrong;
-                    ch = 1;
+    const int nty = tile_row_count(a.rows, kHystTileH);   // tile_grid deals the tile rows over at most kGridMaxYZ workgroup rows
+    for (int by = blockIdx.y; by < nty; by += gridDim.y) {
+        if (by != (int)blockIdx.y) __syncthreads();   // the previous tile is written back before t is loaded again
+        const int x0 = blockIdx.x * kHystTileW, y0 = by * kHystTileH;
+        for (int i = threadIdx.x; i < (kHystTileH + 2) * (kHystTileW + 2); i += blockDim.x) {
+            const int ty = i / (kHystTileW + 2), tx = i % (kHystTileW + 2);
+            const int y = y0 + ty - 1, x = x0 + tx - 1;
+            t[ty][tx] = (y >= 0 && y < a.rows && x >= 0 && x < a.cols) ? lab[(size_t)y * a.lab_pitch + x] : 0;
+        }
+        __syncthreads();
+        // lane -> one segment of one tile row, swept left to right and back, promoting in place: a run along the row is linked in one sweep
+        const int ty = 1 + threadIdx.x / 8, tx0 = 1 + (threadIdx.x % 8) * kHystSeg;
+        int any = 0;
+        for (;;) {
+            int ch = 0;
+            for (int dir = 0; dir < 2; ++dir)
+                for (int j = 0; j < kHystSeg; ++j) {
+                    const int tx = dir ? tx0 + kHystSeg - 1 - j : tx0 + j;
+                    if (t[ty][tx] != kWeak) continue;
+                    const bool hit = t[ty - 1][tx - 1] == kStrong || t[ty - 1][tx] == kStrong || t[ty - 1][tx + 1] == kStrong ||
+                                     t[ty][tx - 1] == kStrong || t[ty][tx + 1] == kStrong || t[ty + 1][tx - 1] == kStrong ||
+                                     t[ty + 1][tx] == kStrong || t[ty + 1][tx + 1] == kStrong;
+                    if (hit) {
+                        t[ty][tx] = kStrong;
+                        ch = 1;
+                    }
                 }
-            }
-        any |= ch;
-        if (!__syncthreads_or(ch)) break;
+            any |= ch;
+            if (!__syncthreads_or(ch)) break;
+        }
+        if (!__syncthreads_or(any)) continue;   // nothing promoted: nothing to write, no flag
+        for (int i = threadIdx.x; i < kHystTileH * kHystTileW; i += blockDim.x) {
+            const int ty2 = i / kHystTileW, tx2 = i % kHystTileW;
+            const int y = y0 + ty2, x = x0 + tx2;
+            if (y < a.rows && x < a.cols) lab[(size_t)y * a.lab_pitch + x] = t[ty2 + 1][tx2 + 1];
+        }
+        if (threadIdx.x == 0) atomicAdd(changed, 1u);
     }
-    if (!__syncthreads_or(any)) return;   // nothing promoted: nothing to write, no flag
-    for (int i = threadIdx.x; i < kHystTileH * kHystTileW; i += blockDim.x) {
-        const int ty2 = i / kHystTileW, tx2 = i % kHystTileW;
-        const int y = y0 + ty2, x = x0 + tx2;
-        if (y < a.rows && x < a.cols) lab[(size_t)y * a.lab_pitch + x] = t[ty2 + 1][tx2 + 1];
-    }
-    if (threadIdx.x == 0) atomicAdd(changed, 1u);
 }
 
 __global__ void k_hyst_flag_reset(unsigned* changed) { *changed = 0u; }
@@ -283,8 +282,8 @@ hipError_t launch_hyst_flag_reset(unsigned* changed, hipStream_t s)
 hipError_t launch_hyst_pass(const HystArgs& a, unsigned* changed, hipStream_t s)
 {
     if (!hyst_ok(a) || !changed) return hipErrorInvalidValue;
-    const dim3 grid((a.cols + kHystTileW - 1) / kHystTileW, (a.rows + kHystTileH - 1) / kHystTileH, a.n);
-    hipLaunchKernelGGL(k_hyst_propagate, grid, dim3(256), 0, s, a, changed);
+    const GridDims gd = tile_grid(a.rows, a.cols, kHystTileW, kHystTileH, a.n);
+    hipLaunchKernelGGL(k_hyst_propagate, dim3(gd.x, gd.y, gd.z), dim3(256), 0, s, a, changed);
     return hipGetLastError();
 }
 

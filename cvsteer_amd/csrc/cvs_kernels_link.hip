@@ -46,58 +46,62 @@ __global__ __launch_bounds__(256) void k_link_tiles(const LinkArgs a)
     const int z = blockIdx.z;
     const LinkDesc d = link_plane(a, z);
     const int rows = a.rows, cols = a.cols;
-    const int x0 = blockIdx.x * kLW, y0 = blockIdx.y * kLH;
-    const int tx = threadIdx.x & (kLW - 1), half = threadIdx.x >> 7, lane = threadIdx.x & 63;
-    const int x = x0 + tx;
     if (a.kept && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) a.kept[z] = 0;
-    unsigned fgbits = 0;
+    const int nty = tile_row_count(rows, kLH);   // tile_grid deals the tile rows over at most kGridMaxYZ workgroup rows
+    for (int by = blockIdx.y; by < nty; by += gridDim.y) {
+        if (by != (int)blockIdx.y) __syncthreads();   // the previous tile's lookups are done before L is written again
+        const int x0 = blockIdx.x * kLW, y0 = by * kLH;
+        const int tx = threadIdx.x & (kLW - 1), half = threadIdx.x >> 7, lane = threadIdx.x & 63;
+        const int x = x0 + tx;
+        unsigned fgbits = 0;
 #pragma unroll
-    for (int k = 0; k < kLH / 2; ++k) {
-        const int ty = 2 * k + half, y = y0 + ty;
-        const bool fg = y < rows && x < cols && d.in[(size_t)y * d.in_pitch + x] > a.low;
-        const unsigned long long gaps = ~__ballot(fg) & ((1ull << lane) - 1ull);   // background lanes left of this one
-        const int start = gaps ? 64 - __clzll((long long)gaps) : 0;                 // first lane of this pixel's run
-        const int i = ty * kLW + tx;
-        L[i] = fg ? i - lane + start : -1;
-        fgbits |= (fg ? 1u : 0u) << k;
-    }
-    __syncthreads();
+        for (int k = 0; k < kLH / 2; ++k) {
+            const int ty = 2 * k + half, y = y0 + ty;
+            const bool fg = y < rows && x < cols && d.in[(size_t)y * d.in_pitch + x] > a.low;
+            const unsigned long long gaps = ~__ballot(fg) & ((1ull << lane) - 1ull);   // background lanes left of this one
+            const int start = gaps ? 64 - __clzll((long long)gaps) : 0;                 // first lane of this pixel's run
+            const int i = ty * kLW + tx;
+            L[i] = fg ? i - lane + start : -1;
+            fgbits |= (fg ? 1u : 0u) << k;
+        }
+        __syncthreads();
 #pragma unroll 1
-    for (int k = 0; k < kLH / 2; ++k) {
-        if (!((fgbits >> k) & 1u)) continue;
-        const int ty = 2 * k + half, i = ty * kLW + tx;
-        const bool up = ty > 0;
-        const bool n = up && lds_get(L, i - kLW) >= 0;
-        const bool nw = up && tx > 0 && lds_get(L, i - kLW - 1) >= 0;
-        const bool ne = up && tx < kLW - 1 && lds_get(L, i - kLW + 1) >= 0;
-        const bool in_run = lane > 0 && lds_get(L, i - 1) >= 0;   // the left neighbour is in this pixel's run (same initial parent)
-        if (!in_run) {
-            if (tx == 64 && lds_get(L, i - 1) >= 0) lds_union(L, i, i - 1);   // the run goes on in the other wave's half of the row
-            if (n) {
-                lds_union(L, i, i - kLW);   // (nw and ne touch n in their own row)
-            } else {
-                if (nw) lds_union(L, i, i - kLW - 1);
-                if (ne) lds_union(L, i, i - kLW + 1);
+        for (int k = 0; k < kLH / 2; ++k) {
+            if (!((fgbits >> k) & 1u)) continue;
+            const int ty = 2 * k + half, i = ty * kLW + tx;
+            const bool up = ty > 0;
+            const bool n = up && lds_get(L, i - kLW) >= 0;
+            const bool nw = up && tx > 0 && lds_get(L, i - kLW - 1) >= 0;
+            const bool ne = up && tx < kLW - 1 && lds_get(L, i - kLW + 1) >= 0;
+            const bool in_run = lane > 0 && lds_get(L, i - 1) >= 0;   // the left neighbour is in this pixel's run (same initial parent)
+            if (!in_run) {
+                if (tx == 64 && lds_get(L, i - 1) >= 0) lds_union(L, i, i - 1);   // the run goes on in the other wave's half of the row
+                if (n) {
+                    lds_union(L, i, i - kLW);   // (nw and ne touch n in their own row)
+                } else {
+                    if (nw) lds_union(L, i, i - kLW - 1);
+                    if (ne) lds_union(L, i, i - kLW + 1);
+                }
+            } else if (!n && ne) {
+                lds_union(L, i, i - kLW + 1);   // every other contact of a pixel inside a run is made by its left neighbour
             }
-        } else if (!n && ne) {
-            lds_union(L, i, i - kLW + 1);   // every other contact of a pixel inside a run is made by its left neighbour
         }
-    }
-    __syncthreads();
-    const size_t base = (size_t)z * a.plane_stride;
+        __syncthreads();
+        const size_t base = (size_t)z * a.plane_stride;
 #pragma unroll 1
-    for (int k = 0; k < kLH / 2; ++k) {
-        const int ty = 2 * k + half, y = y0 + ty;
-        if (y >= rows || x >= cols) continue;
-        int v = -1;
-        if ((fgbits >> k) & 1u) {
-            const int r = lds_find(L, ty * kLW + tx);
-            v = (y0 + r / kLW) * cols + x0 + r % kLW;
+        for (int k = 0; k < kLH / 2; ++k) {
+            const int ty = 2 * k + half, y = y0 + ty;
+            if (y >= rows || x >= cols) continue;
+            int v = -1;
+            if ((fgbits >> k) & 1u) {
+                const int r = lds_find(L, ty * kLW + tx);
+                v = (y0 + r / kLW) * cols + x0 + r % kLW;
+            }
+            const size_t g = base + (size_t)y * cols + x;
+            a.parent[g] = v;
+            a.area[g] = 0;
+            a.peak[g] = 0u;
         }
-        const size_t g = base + (size_t)y * cols + x;
-        a.parent[g] = v;
-        a.area[g] = 0;
-        a.peak[g] = 0u;
     }
 }
 
@@ -110,7 +114,7 @@ __global__ __launch_bounds__(256) void k_link_borders(int rows, int cols, int32_
 {
     int32_t* parent = parent0 + (size_t)blockIdx.y * plane_stride;
     const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
-    const int nty = (rows + kLH - 1) / kLH, ntx = (cols + kLW - 1) / kLW;
+    const int nty = tile_row_count(rows, kLH), ntx = tile_row_count(cols, kLW);
     const long long n_top = (long long)(nty - 1) * cols, n_left = (long long)(ntx - 1) * rows;
     if (id < n_top) {   // (x, y) on the top row of tile row t >= 1: the three neighbours in row y - 1
         const int x = (int)(id % cols), y = (int)(id / cols + 1) * kLH;
@@ -273,16 +277,15 @@ hipError_t launch_link_table(const LinkTableArgs& t, LinkDesc* tab, hipStream_t 
 hipError_t launch_link_tiles(const LinkArgs& a, hipStream_t s)
 {
     if (!link_ok(a)) return hipErrorInvalidValue;
-    const dim3 grid((a.cols + kLW - 1) / kLW, (a.rows + kLH - 1) / kLH, a.n);
-    if (grid.y > 65535u) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_link_tiles, grid, dim3(256), 0, s, a);
+    const GridDims gd = tile_grid(a.rows, a.cols, kLW, kLH, a.n);
+    hipLaunchKernelGGL(k_link_tiles, dim3(gd.x, gd.y, gd.z), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
 hipError_t launch_link_borders(const LinkArgs& a, hipStream_t s)
 {
     if (!link_ok(a)) return hipErrorInvalidValue;
-    const long long nty = (a.rows + kLH - 1) / kLH, ntx = (a.cols + kLW - 1) / kLW;
+    const long long nty = tile_row_count(a.rows, kLH), ntx = tile_row_count(a.cols, kLW);
     const long long lanes = (nty - 1) * a.cols + (ntx - 1) * a.rows;
     const long long blocks = lanes > 0 ? (lanes + 255) / 256 : 1;   // (a single tile: one workgroup that finds nothing to do)
     hipLaunchKernelGGL(k_link_borders, dim3((unsigned)blocks, a.n), dim3(256), 0, s, a.rows, a.cols, a.parent, a.plane_stride);

@@ -648,25 +648,30 @@ __global__ __launch_bounds__(256) void k_pyr_down(const float* src, size_t spitc
                                                    float* dst, size_t dpitch, int orows, int ocols)
 {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int y = (blockIdx.y * 4 + (threadIdx.x >> 6)) * 2;
-    if (x >= ocols || y >= orows) return;
+    if (x >= ocols) return;
     const bool interior = 2 * x - 2 >= 0 && 2 * x + 2 < cols;
-    float r[7];
+    const int groups = pyr_down_group_count(rows);   // groups of eight output rows; pyr_down_grid deals them over at most kGridMaxYZ workgroup rows
+    for (int gy = blockIdx.y; gy < groups; gy += gridDim.y) {
+        const int y = (gy * 4 + (threadIdx.x >> 6)) * 2;
+        if (y >= orows) return;   // (only in the last group)
+        float r[7];
 #pragma unroll
-    for (int j = 0; j < 7; ++j)
-        r[j] = pyr_row<VEC2>(src + (size_t)reflect101(2 * y + j - 2, rows) * spitch, x, cols, interior);
-    const float v0 = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(r[2], 6.0f), __fmul_rn(__fadd_rn(r[1], r[3]), 4.0f)), r[0]), r[4]);
-    dst[(size_t)y * dpitch + x] = __fmul_rn(v0, 1.0f / 256.0f);
-    if (y + 1 < orows) {
-        const float v1 = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(r[4], 6.0f), __fmul_rn(__fadd_rn(r[3], r[5]), 4.0f)), r[2]), r[6]);
-        dst[(size_t)(y + 1) * dpitch + x] = __fmul_rn(v1, 1.0f / 256.0f);
+        for (int j = 0; j < 7; ++j)
+            r[j] = pyr_row<VEC2>(src + (size_t)reflect101(2 * y + j - 2, rows) * spitch, x, cols, interior);
+        const float v0 = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(r[2], 6.0f), __fmul_rn(__fadd_rn(r[1], r[3]), 4.0f)), r[0]), r[4]);
+        dst[(size_t)y * dpitch + x] = __fmul_rn(v0, 1.0f / 256.0f);
+        if (y + 1 < orows) {
+            const float v1 = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(r[4], 6.0f), __fmul_rn(__fadd_rn(r[3], r[5]), 4.0f)), r[2]), r[6]);
+            dst[(size_t)(y + 1) * dpitch + x] = __fmul_rn(v1, 1.0f / 256.0f);
+        }
     }
 }
 
 hipError_t launch_pyr_down(const float* src, size_t spitch, int rows, int cols, float* dst, size_t dpitch, hipStream_t s)
 {
     const int orows = (rows + 1) / 2, ocols = (cols + 1) / 2;
-    const dim3 grid((ocols + 63) / 64, ((orows + 1) / 2 + 3) / 4), block(256);
+    const GridDims gd = pyr_down_grid(rows, cols);
+    const dim3 grid(gd.x, gd.y, gd.z), block(256);
     const bool vec2 = (((uintptr_t)src & 7) == 0) && (spitch % 2 == 0);
     if (vec2) hipLaunchKernelGGL(k_pyr_down<true>, grid, block, 0, s, src, spitch, rows, cols, dst, dpitch, orows, ocols);
     else hipLaunchKernelGGL(k_pyr_down<false>, grid, block, 0, s, src, spitch, rows, cols, dst, dpitch, orows, ocols);

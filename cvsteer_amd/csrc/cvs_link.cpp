@@ -40,8 +40,7 @@ int cvs_link(cvs_handle h, int n, const cvs_plane* in, float low, float high, in
     int rc;
     if ((rc = need_image(h))) return rc;
     const int rows = h->rows, cols = h->cols;
-    if ((long long)rows * cols > 0x7fffffffLL - 1 || (rows + kCcTileH - 1) / kCcTileH > 65535)
-        return fail(h, CVS_E_SIZE, "more than 2^31 - 2 pixels, or more rows than one launch can tile");
+    if ((long long)rows * cols > 0x7fffffffLL - 1) return fail(h, CVS_E_SIZE, "more than 2^31 - 2 pixels");
     const bool u8 = is_u8(&out[0]);
     bool any_host = false;
     for (int k = 0; k < n; ++k) {

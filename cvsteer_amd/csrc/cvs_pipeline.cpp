@@ -140,7 +140,9 @@ int batch_run(cvs_handle h, const cvs_plane* images, int n, const cvs_plane* out
     const size_t pitch = round_up((size_t)cols, 64);
     // one launch over grid.z needs every plane below 2 GiB (huge frames are filtered in row bands, frame by frame)
     const bool small_planes = std::max(max_bytes, (size_t)rows * pitch * sizeof(float)) <= kMaxResourceBytes;
-    const bool fast = (ins_dev || u8_batch) && outs_dev && small_planes &&
+    // ... and a grid inside the bounds of cvs_grid.h whatever order and strip height the launch ends up with (very tall frames, or
+    // more than 65534 of them: frame by frame as well)
+    const bool fast = (ins_dev || u8_batch) && outs_dev && small_planes && strip_batch_fits(rows, cols, h->strip_rows > 0 ? h->strip_rows : 1, n) &&
                       !basis_may_need_scratch(h->kind, h->width, h->taps, rows, cols, std::max(pitch, max_bytes / sizeof(float) / rows));
     if (!fast && u8) return kNotFused;
     if (!fast) {
@@ -208,6 +210,7 @@ int batch_run(cvs_handle h, const cvs_plane* images, int n, const cvs_plane* out
     fill_state_args(h, a, true);   // frame 0 (cur_frame was reset above); frame z adds z * frame_stride in the kernel
     a.atan_mode = h->atan_mode;
     a.strip_rows = default_strip_rows(h, rows, cols);
+    a.block_order = h->block_order >= 0 ? h->block_order : 0;   // the default's order (default_config)
     a.nt_stores = use_nt_stores(h, (size_t)rows * cols * n);
     a.pipe = 1;
     a.no_state = h->persist ? 0 : 1;

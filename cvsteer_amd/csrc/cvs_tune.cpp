@@ -147,6 +147,10 @@ static bool fits(const BasisArgs& a, const Cand& c)
     const int grid_x = ((a.cols + 63) / 64 + 3) / 4;
     if (c.order == kOrderXcdColumns && (grid_x % 8 != 0 || a.batch != 0)) return false;
     if (c.order == kOrderDynamic && !a.tile_ctr) return false;
+    // 8-bit outputs exist in ONE fused launch only, and the API layer has judged this launch to be one with the default's order and strip
+    // height (basis_u8_fusable, before the tuner is asked): a candidate under which the grid bound of cvs_grid.h would split it into row
+    // bands (shorter strips on a tall image, another order) does not fit -- the default runs
+    if (a.u8_mode && a.batch == 0 && !strip_one_launch(c.order, a.cols, c.strip, 1u, a.rows)) return false;
     return true;
 }
 

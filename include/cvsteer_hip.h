@@ -617,8 +617,8 @@ int cvs_polyline_segments(cvs_handle h,
  * the size it needs (the same call, made once eagerly, sees to that); otherwise CVS_E_UNSUPPORTED, and the handle works on.  Host
  * planes are staged on the device, at most eight planes per chain, synchronise, and are refused during capture.
  * low > high, a NaN threshold, min_area < 0, NaN min_peak, n < 1, outputs of mixed depth, any overlap of an output with an input or
- * another output: CVS_E_BADARG; a plane of another size than the handle's image: CVS_E_SIZE; no image size yet: CVS_E_STATE.  Nothing
- * is written when an argument is rejected. */
+ * another output: CVS_E_BADARG; a plane of another size than the handle's image, or rows * cols > 2^31 - 2 (the limit of cvs_label, and
+ * the only one: any height goes): CVS_E_SIZE; no image size yet: CVS_E_STATE.  Nothing is written when an argument is rejected. */
 int cvs_link(cvs_handle h, int n, const cvs_plane* in, float low, float high, int min_area, float min_peak,
              const cvs_plane* out, int32_t* kept_dev);
 
