@@ -17,6 +17,12 @@
  *    (CVS_MEM_DEVICE).  cv::Mat1f maps 1:1: {(float*)m.data, m.rows, m.cols, m.step}.
  *  - a handle owns its state planes (basis, C1..C3, theta, strength) in device memory;
  *    callers own every plane they pass in.  State stays valid until the next cvs_setup.
+ *  - a plane may be a region of interest of a larger image (step > row length), and then the rest of that image is the caller's
+ *    too: (1) a call writes exactly rows x cols elements of each output plane and not one byte more -- not the padding of a row,
+ *    not a row above or below the view; (2) a call never writes to an input (unless the caller passes it as an output too,
+ *    where that is allowed); (3) what lies around an input view never changes a result.  This holds for host and device
+ *    planes, for 8-bit (CVS_DEPTH_U8) and int32 (CVS_DEPTH_S32) planes, and for the arrays that come with a capacity or a count:
+ *    nothing in front of the array and nothing behind its last element is written.
  *  - all device work is enqueued on the handle's HIP stream (default: the null stream;
  *    cvs_set_stream to share e.g. PyTorch's current stream).  Calls with only DEVICE planes
  *    are asynchronous; calls that touch a HOST plane return after the data has landed.
