@@ -68,6 +68,25 @@ class Segment(C.Structure):
 
 
 SEG_WRAPS, SEG_DEGENERATE = 1, 2
+
+
+class TurnCfg(C.Structure):
+    """struct cvs_turn_cfg"""
+    _fields_ = [("radius", C.c_int32), ("min_arm", C.c_int32), ("nms", C.c_int32), ("max_cos", C.c_float)]
+
+
+class ChainTurn(C.Structure):
+    """struct cvs_chain_turn"""
+    _fields_ = [("chain", C.c_int32), ("flags", C.c_int32), ("nb", C.c_int32), ("nf", C.c_int32),
+                ("sin", C.c_float), ("cos", C.c_float), ("lb", C.c_float), ("lf", C.c_float)]
+
+
+class TurnSummary(C.Structure):
+    """struct cvs_turn_summary"""
+    _fields_ = [("corners", C.c_int32), ("eligible", C.c_int32), ("sharpest", C.c_int32), ("min_cos", C.c_float)]
+
+
+TURN_CORNER, TURN_END, TURN_DEGENERATE, TURN_SHORT, TURN_NO_CHAIN = 1, 2, 4, 8, 16
 PEAKS_MAX = 4
 
 
@@ -128,6 +147,8 @@ SIGNATURES = {
     "cvs_chain_measures": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "cvs_polyline_segments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_int]),
+    "cvs_chain_turns": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(TurnCfg), C.c_void_p, C.c_void_p,
+                                  C.c_int]),
     "cvs_contour_chains_batch": (C.c_int, [C.c_void_p, C.c_int, _PP, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, _IP, _IP]),
     "cvs_chain_refine_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _PP, _PP, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_int]),

@@ -902,6 +902,67 @@ class _CallerPipeline:
                           seg["cx"] + seg["t1"] * seg["ux"], seg["cy"] + seg["t1"] * seg["uy"]], axis=1).reshape(-1, 4)
         return seg, lines
 
+    # -- contour turns (extension beyond the reference): cvs_chain_turns --
+    TURN_DTYPE = np.dtype([("chain", "<i4"), ("flags", "<i4"), ("nb", "<i4"), ("nf", "<i4"), ("sin", "<f4"), ("cos", "<f4"), ("lb", "<f4"),
+                           ("lf", "<f4")])
+    TURN_SUMMARY_DTYPE = np.dtype([("corners", "<i4"), ("eligible", "<i4"), ("sharpest", "<i4"), ("min_cos", "<f4")])
+
+    def chain_turns(self, points, chains, xy=None, radius=5, min_arm=None, nms=None, max_cos=0.70710678, summary=False, out=None):
+        """One record per chain point (cvs_chain_turns): a numpy structured array with the fields of `cvs_chain_turn` -- record i holds the
+        turn of the contour at point i between the direction towards it from the centroid of the `radius` points before it and the
+        direction from it to the centroid of the `radius` points after it (chain, flags, the arm sizes nb and nf, sin and cos of the turn,
+        the arm lengths lb and lf); flags & TURN_CORNER marks the corners: eligible points (both arms of min_arm points or more) with
+        cos <= max_cos that are the sharpest within `nms` points either way, the first of a plateau.  min_arm and nms default to radius,
+        max_cos to cos 45 deg.  points (N, 2) int32 and chains (M, 4) int32 as contour_chains returns them, xy (N, 2) float32 as
+        chain_refine does: xy=None takes the integer points.  summary=True returns (turns, summary), the second a structured array with
+        the fields of `cvs_turn_summary`, one per chain.  Torch CUDA arrays take the device path: the tables are written on the device
+        and downloaded for the return value -- or, with out= an (N, 32) uint8 CUDA tensor (summary=True: a pair with an (M, 16) one), left
+        there (two or three launches, nothing read back, capturable; out.cpu().numpy().view(TURN_DTYPE) reads it) and `out` is returned.
+        numpy arrays and torch CPU tensors take the host path.  include/cvsteer_hip.h has the contract."""
+        dev = _is_torch(points) and points.is_cuda
+        points = self._chain_array(points, dev, np.int32, 2, "points")
+        chains = self._chain_array(chains, dev, np.int32, 4, "chains")
+        xy = self._chain_array(xy, dev, np.float32, 2, "xy")
+        n, m = int(points.shape[0]), int(chains.shape[0])
+        if xy is not None and xy.shape[0] != n:
+            raise ValueError("xy: one entry per point")
+        cfg = L.TurnCfg(int(radius), int(radius if min_arm is None else min_arm), int(radius if nms is None else nms), float(max_cos))
+        size, ssize = self.TURN_DTYPE.itemsize, self.TURN_SUMMARY_DTYPE.itemsize
+        sums = None
+        if out is not None:
+            table, sums = out if summary else (out, None)
+            if not (dev and self._is_out(table, dev, np.uint8, (n, size)) and (not summary or self._is_out(sums, dev, np.uint8, (m, ssize)))):
+                raise ValueError("out: a contiguous (N, %d) uint8 CUDA tensor%s, with device arrays"
+                                 % (size, " and an (M, %d) one" % ssize if summary else ""))
+        elif dev:
+            table = torch.empty((n, size), dtype=torch.uint8, device=points.device)
+            sums = torch.empty((m, ssize), dtype=torch.uint8, device=points.device) if summary else None
+        else:
+            table = np.zeros(n, self.TURN_DTYPE)
+            sums = np.zeros(m, self.TURN_SUMMARY_DTYPE) if summary else None
+        if dev:
+            self._bind_stream(points)
+        self._check(lib().cvs_chain_turns(self._h, self._array_ptr(points), n, self._array_ptr(chains), m, self._array_ptr(xy), C.byref(cfg),
+                                          self._array_ptr(table), self._array_ptr(sums), L.MEM_DEVICE if dev else L.MEM_HOST), "cvs_chain_turns")
+        if out is not None:
+            return out
+        if dev:
+            table = table.cpu().numpy().view(self.TURN_DTYPE).reshape(n)
+            sums = sums.cpu().numpy().view(self.TURN_SUMMARY_DTYPE).reshape(m) if summary else None
+        return (table, sums) if summary else table
+
+    def contour_corners(self, mask, map, theta=None, **cfg):
+        """The corners of the linked contours of a mask: contour_chains(mask) -> chain_refine on the un-thinned `map` the mask came from ->
+        chain_turns on the refined positions (**cfg: its radius, min_arm, nms and max_cos).  Returns (corner_xy, corner_index, turns,
+        chains): the (K, 2) float32 sub-pixel positions of the corners, their (K,) positions in the point list, the record of every
+        point and the chain table."""
+        points, chains = self.contour_chains(mask)
+        xy, _ = self.chain_refine(points, map, theta)
+        turns = self.chain_turns(points, chains, xy=xy, **cfg)
+        index = np.nonzero(turns["flags"] & L.TURN_CORNER)[0]
+        host_xy = xy.cpu().numpy() if _is_torch(xy) else np.asarray(xy)
+        return host_xy[index], index, turns, chains
+
     def contours(self, image, low, high, min_area=0, min_peak=0.0):
         """Thin, linked contours of one image: pipeline(image) -> nonmax(edges, dark, bright) on the object's own theta ->
         hysteresis(low, high).  Returns three uint8 masks (edges, dark lines, bright lines).  min_area > 0 or min_peak > 0: the

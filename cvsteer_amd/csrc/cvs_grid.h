@@ -34,6 +34,14 @@ inline GridDims generic_grid(int rows, int cols)
     return {(unsigned)grid_ceil_div(cols, 256), grid_cap_yz(rows), 1u};
 }
 
+// ---- one workgroup per `per` entries of a LIST (points, chains): x alone, held to kGridMaxX; the kernel strides the list with
+// gridDim.x * per (k_turn_summary) or shows that its list never reaches the bound (k_turns, k_turn_nms: 2^30 points / 256) ----
+inline GridDims list_grid(long long n, int per)
+{
+    const long long g = grid_ceil_div(n, per);
+    return {g < 1 ? 1u : g > (long long)kGridMaxX ? kGridMaxX : (unsigned)g, 1u, 1u};
+}
+
 // ---- one workgroup per tile_w x tile_h tile and plane; the kernel strides the tile rows (k_cc_tiles, k_link_tiles, k_ch_links,
 // k_hyst_propagate, k_chb_links, k_chb_tiles) ----
 constexpr int tile_row_count(int rows, int tile_h) { return (int)grid_ceil_div(rows, tile_h); }

@@ -232,6 +232,52 @@ int fit_segments(cvs_handle h, const Mat1f& response, const std::vector<std::vec
     return CVS_OK;
 }
 
+// refine_contours on the handle's own theta and cvs_chain_turns on its result, one packing for the two calls; the host loop only sorts the
+// corner records into their chains
+int corner_contours(cvs_handle h, const Mat1f& response, const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags, int radius,
+                    float maxCosine, std::vector<std::vector<int> >& corners, std::vector<std::vector<float> >* cosines, int* n)
+{
+    if (flags && flags->size() != chains.size()) return CVS_E_BADARG;
+    size_t np = 0;
+    for (size_t c = 0; c < chains.size(); ++c) np += chains[c].size();
+    if (np > (size_t)1 << 30) return CVS_E_SIZE;
+    std::vector<int32_t> pts(np * 2);
+    std::vector<float> xy(np * 2);
+    std::vector<cvs_chain> tab(chains.size());
+    size_t at = 0;
+    for (size_t c = 0; c < chains.size(); ++c) {
+        tab[c].start = (int32_t)at;
+        tab[c].length = (int32_t)chains[c].size();
+        tab[c].flags = flags ? (*flags)[c] : 0;
+        tab[c].reserved = 0;
+        for (size_t k = 0; k < chains[c].size(); ++k, ++at) {
+            pts[2 * at] = chains[c][k].x;
+            pts[2 * at + 1] = chains[c][k].y;
+        }
+    }
+    cvs_plane pr = view(response);
+    int rc = cvs_chain_refine(h, &pr, 0, pts.data(), (int)np, xy.data(), 0, CVS_MEM_HOST);
+    if (rc != CVS_OK) return rc;
+    cvs_turn_cfg cfg;
+    cfg.radius = cfg.min_arm = cfg.nms = radius;
+    cfg.max_cos = maxCosine;
+    std::vector<cvs_chain_turn> turns(np);
+    if ((rc = cvs_chain_turns(h, pts.data(), (int)np, tab.data(), (int)chains.size(), xy.data(), &cfg, turns.data(), 0, CVS_MEM_HOST)) != CVS_OK)
+        return rc;
+    corners.assign(chains.size(), std::vector<int>());
+    if (cosines) cosines->assign(chains.size(), std::vector<float>());
+    int count = 0;
+    for (size_t i = 0; i < np; ++i) {
+        const cvs_chain_turn& t = turns[i];
+        if (!(t.flags & CVS_TURN_CORNER)) continue;
+        corners[(size_t)t.chain].push_back((int)(i - (size_t)tab[(size_t)t.chain].start));
+        if (cosines) (*cosines)[(size_t)t.chain].push_back(t.cos);
+        ++count;
+    }
+    *n = count;
+    return CVS_OK;
+}
+
 }  // namespace
 
 // --------------------------------------------------------------------------- base
@@ -507,6 +553,15 @@ int SteerableFiltersG2::fitSegments(const Mat1f& response, const std::vector<std
     return n;
 }
 
+int SteerableFiltersG2::cornerContours(const Mat1f& response, const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags,
+                                       int radius, float maxCosine, std::vector<std::vector<int> >& corners,
+                                       std::vector<std::vector<float> >* cosines)
+{
+    int n = 0;
+    check(corner_contours(m_handle, response, chains, flags, radius, maxCosine, corners, cosines, &n), "cvs_chain_turns");
+    return n;
+}
+
 void SteerableFiltersG2::phaseWeights(const Mat1f& phase, Mat1f& lambda, float phi, bool signum, float k)
 {
     std::lock_guard<std::mutex> lock(g_static_mutex);
@@ -673,6 +728,15 @@ int SteerableFiltersG4::fitSegments(const Mat1f& response, const std::vector<std
 {
     int n = 0;
     check(fit_segments(m_handle, response, chains, flags, epsilon, lines, rms, &n), "cvs_polyline_segments");
+    return n;
+}
+
+int SteerableFiltersG4::cornerContours(const Mat1f& response, const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags,
+                                       int radius, float maxCosine, std::vector<std::vector<int> >& corners,
+                                       std::vector<std::vector<float> >* cosines)
+{
+    int n = 0;
+    check(corner_contours(m_handle, response, chains, flags, radius, maxCosine, corners, cosines, &n), "cvs_chain_turns");
     return n;
 }
 

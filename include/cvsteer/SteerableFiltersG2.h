@@ -93,6 +93,12 @@ public:
     // approxContours.  Returns the number of segments
     int fitSegments(const Mat1f& response, const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags, float epsilon,
                     std::vector<std::vector<float> >& lines, std::vector<std::vector<float> >* rms = 0);
+    // contour turns (extension, cvs_chain_turns): the corners of the chains -- refineContours on `response`, then the turn of the contour
+    // at every point between the centroids of the `radius` points before and after it, by the contract of include/cvsteer_hip.h with
+    // min_arm = nms = radius and max_cos = maxCosine.  corners[c] = the offsets into chains[c] of its corners, ascending; cosines
+    // (optional): cosines[c] = the cosine of the turn at each of them.  flags as in approxContours.  Returns the number of corners
+    int cornerContours(const Mat1f& response, const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags, int radius,
+                       float maxCosine, std::vector<std::vector<int> >& corners, std::vector<std::vector<float> >* cosines = 0);
 
 protected:
     // the reference's protected members, same names (SteerableFiltersG2.h:62-66).  m_g1..m_h4 are the 7 tap vectors; the

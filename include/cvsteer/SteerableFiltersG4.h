@@ -51,6 +51,10 @@ public:
     // theta and throws where the object has no orientation state)
     int fitSegments(const Mat1f& response, const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags, float epsilon,
                     std::vector<std::vector<float> >& lines, std::vector<std::vector<float> >* rms = 0);
+    // addition: the corners of the chains, as in SteerableFiltersG2 (cvs_chain_turns; it refines on the object's own theta and throws where
+    // the object has no orientation state)
+    int cornerContours(const Mat1f& response, const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags, int radius,
+                       float maxCosine, std::vector<std::vector<int> >& corners, std::vector<std::vector<float> >* cosines = 0);
 
 protected:
     // the reference's protected members, same names (SteerableFiltersG4.h:50-56): 11 tap vectors; the planes m_g4a..m_h4f

@@ -601,6 +601,84 @@ int cvs_polyline_segments(cvs_handle h,
         cvs_segment* table,     /* n_vertices records */
         int mem);
 
+/* EXTENSION: contour turns -- table[i] says how sharply the contour turns at point i of a point list, and whether the point is a CORNER of
+ * its chain: the turn between the direction in which the chain arrives (from the centroid of the `radius` points before it) and the one in
+ * which it leaves (towards the centroid of the `radius` points after it).  One fixed-size record per input point, so the table lines up
+ * with `points`: no count, no prefix sum, nothing read back.  Needs no image size (any handle, before or after a setup).  No curvature is
+ * stored: the record carries the sine, the cosine and the two arm lengths, from which a caller forms what it wants.
+ * ARMS.  Point i lies in chain c = (S, L, F) = chains[c] at offset j = i - S.  Open chain: nb = min(radius, j), nf = min(radius, L-1-j); the
+ * arm points are the offsets j-k, k = 1 .. nb, and j+k, k = 1 .. nf.  Chain with CVS_CHAIN_CLOSED: nb = nf = min(radius, (L-1)/2) (integer
+ * division) and the offsets are taken modulo L, so the two arms never share a point and never contain j itself.
+ * SUMS.  All arithmetic is IEEE double, every operation rounded on its own (no contraction).  The coordinates (x, y) of a point are its
+ * (xs, ys) pair of `xy` widened to double when xy != NULL, else its integer point.  Term k of the backward arm is
+ * (x[j-k] - x[j], y[j-k] - y[j]); sb = term 1 + term 2 + ... + term nb, added in ascending k, x and y separately; sf the same over j+k.
+ * ab = sb / (double)nb, af = sf / (double)nf (component by component, correctly rounded): the arm centroids relative to the point.
+ * TURN.  din = (-ab.x, -ab.y); cr = din.x*af.y - din.y*af.x; dt = din.x*af.x + din.y*af.y; la = sqrt(ab.x*ab.x + ab.y*ab.y),
+ * lf = sqrt(af.x*af.x + af.y*af.y) (sqrt correctly rounded); den = la*lf.  Stored: sin = (float)(cr/den), cos = (float)(dt/den),
+ * lb = (float)la, lf = (float)lf; nothing is clamped (|sin|, |cos| may exceed 1 by a rounding).  cos = 1 is a straight chain, 0 a right
+ * angle, -1 a reversal.  x grows to the right and y DOWNWARDS, as in every point list here: a positive sine is a CLOCKWISE turn as seen
+ * on the screen -- to the right for someone who walks along the chain in its direction -- and a negative one counter-clockwise.
+ * FLAGS.  CVS_TURN_END: nb == 0 or nf == 0 (every point of a chain with L == 1, both points of an open chain with L == 2, all points of a
+ * closed chain with L <= 2, the two ends of every open chain): sin and cos are NaN, the length of a missing arm is 0 and that of an arm
+ * that exists is as computed.  CVS_TURN_DEGENERATE: not END, and !(den > 0) or den is not finite (an arm centroid on the point itself, a
+ * NaN or an infinity in xy): sin and cos are NaN, lb and lf as computed.  CVS_TURN_SHORT: nb < min_arm or nf < min_arm (set beside END as
+ * well).  Every NaN the call stores is the quiet NaN 0x7FC00000.  A point is ELIGIBLE iff none of END, DEGENERATE, SHORT and NO_CHAIN
+ * (below) is set; the cos of an eligible point is finite.
+ * CORNER.  CVS_TURN_CORNER is set iff the point is eligible, its stored cos <= max_cos (float comparison), and for every k = 1 .. nms
+ * (closed chains: k <= (L-1)/2 as well) whose neighbour at offset j-k / j+k exists and is eligible: cos_i < cos_(j-k) (strict backwards)
+ * and cos_i <= cos_(j+k).  Open chains skip offsets outside [0, L); closed chains wrap modulo L.  This is the plateau rule of cvs_nonmax
+ * applied to the smaller cosine: of equal cosines side by side the first wins (on a closed chain whose equal minima follow each other
+ * within nms all the way round none is the first, and none is a corner).  A point that is not eligible is never a corner and never
+ * suppresses one.  nms == 0: every eligible point with cos <= max_cos is a corner.
+ * SUMMARY (may be NULL).  summary[c]: corners / eligible = the number of points of chain c with CVS_TURN_CORNER / that are eligible;
+ * sharpest = the position in `points` of the eligible point with the smallest cos, the first on ties, -1 if there is none; min_cos = that
+ * cos, +INFINITY if there is none.  Only records whose `chain` is c count.  Integers and a minimum with a first-index tie rule: the order
+ * of evaluation does not matter.
+ * TABLES.  The chain of point i is the largest c with chains[c].start <= i (the rule of cvs_polyline_segments).  HOST tables are checked
+ * in full: CVS_E_BADARG unless the starts are the running sum of the lengths from 0 to n_points and every length is >= 1 (so n_points > 0
+ * needs n_chains > 0).  DEVICE tables are trusted for their meaning only: the search is a binary search that cannot leave
+ * 0 .. n_chains - 1 and finds that c whenever the starts ascend (which entry it finds where they do not is unspecified); a point that does
+ * not lie inside the entry found -- S < 0, L < 1, S + L > n_points, i < S or i >= S + L -- gets chain -1, flags CVS_TURN_NO_CHAIN, nb =
+ * nf = 0, lb = lf = 0 and NaN in sin and cos, and an entry that fails the first three conditions gets the summary of a chain without
+ * points (0, 0, -1, +INFINITY).  So no load leaves the arrays; coordinates are never used as addresses.  A table of
+ * cvs_contour_chains_batch goes through as it is: its starts are global, and `reserved` is not read.
+ * points, chains, xy, table and summary are all in host or all in device memory (mem).  Device arrays: two launches, three with summary
+ * -- one lane per point for the turns, one lane per point for the corners, one wave per chain of up to 256 points and one 256-lane
+ * workgroup per longer chain for the summary -- queued on the handle's stream, nothing read back, capturable; the launch sequence depends
+ * on (n_points, n_chains, summary != NULL) alone.  The result is a function of the inputs alone: the same call twice gives the same
+ * bytes.  No floating-point atomic is used.  Host arrays are staged in handle scratch (grown only, freed by cvs_destroy), the call
+ * synchronises, and it returns CVS_E_UNSUPPORTED while the stream is being captured.  n_points == 0: CVS_OK, nothing queued and nothing
+ * written (summary included).
+ * CVS_E_BADARG, nothing written: cfg NULL, radius outside 1 .. 64, min_arm outside 1 .. radius, nms outside 0 .. 64, max_cos NaN or outside
+ * -1 .. 1; a negative count; a required array missing (points / table with n_points > 0, chains with n_chains > 0); n_points > 0 with
+ * n_chains == 0; an invalid mem; a pointer not aligned to 4 bytes; table or summary overlapping an input or each other; a HOST table as
+ * above.  n_points > 2^30: CVS_E_SIZE. */
+typedef struct cvs_turn_cfg {
+    int32_t radius;    /* 1..64: points per arm */
+    int32_t min_arm;   /* 1..radius: a point with a shorter arm is never a corner and never suppresses one */
+    int32_t nms;       /* 0..64: half window of the 1-D non-maximum suppression; 0 = none */
+    float   max_cos;   /* a corner has cos <= max_cos; -1..1, NaN refused */
+} cvs_turn_cfg;
+typedef struct cvs_chain_turn {      /* 32 bytes */
+    int32_t chain;                   /* the chain the point belongs to; -1: none (device tables only) */
+    int32_t flags;                   /* CVS_TURN_CORNER = 1, CVS_TURN_END = 2, CVS_TURN_DEGENERATE = 4, CVS_TURN_SHORT = 8, CVS_TURN_NO_CHAIN = 16 */
+    int32_t nb, nf;                  /* points in the backward / forward arm */
+    float   sin, cos;                /* of the turn from the incoming to the outgoing direction; sin > 0: clockwise on the screen */
+    float   lb, lf;                  /* distance of the arm centroids from the point */
+} cvs_chain_turn;
+enum { CVS_TURN_CORNER = 1, CVS_TURN_END = 2, CVS_TURN_DEGENERATE = 4, CVS_TURN_SHORT = 8, CVS_TURN_NO_CHAIN = 16 };
+typedef struct cvs_turn_summary {    /* 16 bytes, one per chain */
+    int32_t corners, eligible;       /* points of the chain with CVS_TURN_CORNER / that are eligible */
+    int32_t sharpest;                /* position in `points` of the eligible point with the smallest cos, the first on ties; -1 */
+    float   min_cos;                 /* +INFINITY if none */
+} cvs_turn_summary;
+int cvs_chain_turns(cvs_handle h, const int32_t* points, int n_points, const cvs_chain* chains, int n_chains,
+                    const float* xy,            /* NULL: the integer points */
+                    const cvs_turn_cfg* cfg,
+                    cvs_chain_turn* table,      /* n_points records */
+                    cvs_turn_summary* summary,  /* NULL, or n_chains records */
+                    int mem);
+
 /* ---- EXTENSION beyond the reference: the contour chain on the batch axis -- cvs_link, cvs_nonmax_batch, cvs_contours_batch ----
  * None of the three reads anything back: with device planes they queue a launch sequence that depends on the image size, the number of
  * planes and how the planes lie in memory (one constant stride, or not) -- never on what the planes hold -- and return. */
