@@ -87,6 +87,20 @@ class TurnSummary(C.Structure):
 
 
 TURN_CORNER, TURN_END, TURN_DEGENERATE, TURN_SHORT, TURN_NO_CHAIN = 1, 2, 4, 8, 16
+
+
+class JoinCfg(C.Structure):
+    """struct cvs_join_cfg"""
+    _fields_ = [("radius", C.c_int32), ("min_arm", C.c_int32), ("min_cos", C.c_float), ("reserved", C.c_int32)]
+
+
+class ChainJoin(C.Structure):
+    """struct cvs_chain_join"""
+    _fields_ = [("node", C.c_int32), ("degree", C.c_int32), ("next", C.c_int32), ("partner", C.c_int32), ("flags", C.c_int32), ("n", C.c_int32),
+                ("cos", C.c_float), ("sin", C.c_float)]
+
+
+JOIN_MUTUAL, JOIN_NONE, JOIN_CROWDED, JOIN_SHORT, JOIN_DEGENERATE, JOIN_NO_CHAIN = 1, 2, 4, 8, 16, 32
 PEAKS_MAX = 4
 
 
@@ -149,6 +163,7 @@ SIGNATURES = {
                                         C.c_void_p, C.c_void_p, C.c_int]),
     "cvs_chain_turns": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(TurnCfg), C.c_void_p, C.c_void_p,
                                   C.c_int]),
+    "cvs_chain_joins": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(JoinCfg), C.c_void_p, C.c_int]),
     "cvs_contour_chains_batch": (C.c_int, [C.c_void_p, C.c_int, _PP, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, _IP, _IP]),
     "cvs_chain_refine_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _PP, _PP, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_int]),

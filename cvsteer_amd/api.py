@@ -963,6 +963,53 @@ class _CallerPipeline:
         host_xy = xy.cpu().numpy() if _is_torch(xy) else np.asarray(xy)
         return host_xy[index], index, turns, chains
 
+    # -- contour joins (extension beyond the reference): cvs_chain_joins --
+    JOIN_DTYPE = np.dtype([("node", "<i4"), ("degree", "<i4"), ("next", "<i4"), ("partner", "<i4"), ("flags", "<i4"), ("n", "<i4"), ("cos", "<f4"),
+                           ("sin", "<f4")])
+
+    def chain_joins(self, points, chains, xy=None, radius=8, min_arm=None, min_cos=-1.0, out=None):
+        """Two records per chain (cvs_chain_joins): a numpy structured array with the fields of `cvs_chain_join` -- record 2c is the head of
+        chain c, record 2c + 1 its tail.  node, degree and next say which chain ends share the end's pixel (the smallest end number there,
+        how many there are, the next one in the ring); partner is the end there that continues this one most nearly straight, judged on
+        arms of up to `radius` points, cos and sin the turn from this end into it; flags & JOIN_MUTUAL marks the joins both ends agree on
+        with cos >= min_cos.  An end whose arm has fewer than min_arm points (default min(3, radius)) joins nothing.  points (N, 2) int32
+        and chains (M, 4) int32 as contour_chains or contour_chains_batch return them (ends of different planes never meet), xy (N, 2)
+        float32 as chain_refine does: xy=None takes the integer points.  Torch CUDA arrays take the device path: the table is written on
+        the device and downloaded for the return value -- or, with out= a (2M, 32) uint8 CUDA tensor, left there (three launches, nothing
+        read back, capturable once the handle's scratch has its size; out.cpu().numpy().view(JOIN_DTYPE) reads it) and `out` is returned.
+        numpy arrays and torch CPU tensors take the host path.  include/cvsteer_hip.h has the contract."""
+        dev = _is_torch(points) and points.is_cuda
+        points = self._chain_array(points, dev, np.int32, 2, "points")
+        chains = self._chain_array(chains, dev, np.int32, 4, "chains")
+        xy = self._chain_array(xy, dev, np.float32, 2, "xy")
+        n, m = int(points.shape[0]), int(chains.shape[0])
+        if xy is not None and xy.shape[0] != n:
+            raise ValueError("xy: one entry per point")
+        cfg = L.JoinCfg(int(radius), int(min(3, radius) if min_arm is None else min_arm), float(min_cos), 0)
+        size = self.JOIN_DTYPE.itemsize
+        if out is not None:
+            if not (dev and self._is_out(out, dev, np.uint8, (2 * m, size))):
+                raise ValueError("out: a contiguous (2 M, %d) uint8 CUDA tensor, with device arrays" % size)
+            table = out
+        elif dev:
+            table = torch.empty((2 * m, size), dtype=torch.uint8, device=points.device)
+        else:
+            table = np.zeros(2 * m, self.JOIN_DTYPE)
+        if dev:
+            self._bind_stream(points)
+        self._check(lib().cvs_chain_joins(self._h, self._array_ptr(points), n, self._array_ptr(chains), m, self._array_ptr(xy), C.byref(cfg),
+                                          self._array_ptr(table), L.MEM_DEVICE if dev else L.MEM_HOST), "cvs_chain_joins")
+        if out is not None or not dev:
+            return table
+        return table.cpu().numpy().view(self.JOIN_DTYPE).reshape(2 * m)
+
+    def contour_joins(self, mask, map, theta=None, **cfg):
+        """The joins of the linked contours of a mask: contour_chains(mask) -> chain_refine on the un-thinned `map` the mask came from ->
+        chain_joins on the refined positions (**cfg: its radius, min_arm and min_cos).  Returns (joins, points, chains, xy)."""
+        points, chains = self.contour_chains(mask)
+        xy, _ = self.chain_refine(points, map, theta)
+        return self.chain_joins(points, chains, xy=xy, **cfg), points, chains, xy
+
     def contours(self, image, low, high, min_area=0, min_peak=0.0):
         """Thin, linked contours of one image: pipeline(image) -> nonmax(edges, dark, bright) on the object's own theta ->
         hysteresis(low, high).  Returns three uint8 masks (edges, dark lines, bright lines).  min_area > 0 or min_peak > 0: the

@@ -1,5 +1,5 @@
 // cvs_contour_host.h -- what the host units of the contour tail share in front of their kernels (cvs_contour.cpp, which defines it,
-// cvs_components.cpp, cvs_link.cpp, cvs_chains.cpp, cvs_chains_batch.cpp, cvs_polyline.cpp, cvs_refine.cpp, cvs_segments.cpp, cvs_turns.cpp): the checks every entry point begins with, the handle's scratch as a
+// cvs_components.cpp, cvs_link.cpp, cvs_chains.cpp, cvs_chains_batch.cpp, cvs_polyline.cpp, cvs_refine.cpp, cvs_segments.cpp, cvs_turns.cpp, cvs_joins.cpp): the checks every entry point begins with, the handle's scratch as a
 // bump allocator, and the routes of mask inputs and mask outputs.  Internal; the overlap rule of the tail is check_disjoint (cvs_context.h).
 #pragma once
 #include <algorithm>

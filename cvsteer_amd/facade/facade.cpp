@@ -8,6 +8,7 @@
 #include <cvsteer/SteerableFiltersG4.h>
 
 #include <cstddef>
+#include <limits>
 #include <mutex>
 #include <stdexcept>
 #include <string>
@@ -273,6 +274,54 @@ int corner_contours(cvs_handle h, const Mat1f& response, const std::vector<std::
         corners[(size_t)t.chain].push_back((int)(i - (size_t)tab[(size_t)t.chain].start));
         if (cosines) (*cosines)[(size_t)t.chain].push_back(t.cos);
         ++count;
+    }
+    *n = count;
+    return CVS_OK;
+}
+
+// refine_contours on the handle's own theta and cvs_chain_joins on its result, one packing for the two calls; the host loop only copies the
+// partners of the mutual joins out of the records
+int join_contours(cvs_handle h, const Mat1f& response, const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags, int radius,
+                  float minCosine, std::vector<int>& partners, std::vector<float>* cosines, int* n)
+{
+    if (flags && flags->size() != chains.size()) return CVS_E_BADARG;
+    size_t np = 0;
+    for (size_t c = 0; c < chains.size(); ++c) np += chains[c].size();
+    if (np > (size_t)1 << 30 || chains.size() > (size_t)1 << 26) return CVS_E_SIZE;
+    std::vector<int32_t> pts(np * 2);
+    std::vector<float> xy(np * 2);
+    std::vector<cvs_chain> tab(chains.size());
+    size_t at = 0;
+    for (size_t c = 0; c < chains.size(); ++c) {
+        tab[c].start = (int32_t)at;
+        tab[c].length = (int32_t)chains[c].size();
+        tab[c].flags = flags ? (*flags)[c] : 0;
+        tab[c].reserved = 0;
+        for (size_t k = 0; k < chains[c].size(); ++k, ++at) {
+            pts[2 * at] = chains[c][k].x;
+            pts[2 * at + 1] = chains[c][k].y;
+        }
+    }
+    cvs_plane pr = view(response);
+    int rc = cvs_chain_refine(h, &pr, 0, pts.data(), (int)np, xy.data(), 0, CVS_MEM_HOST);
+    if (rc != CVS_OK) return rc;
+    cvs_join_cfg cfg;
+    cfg.radius = radius;
+    cfg.min_arm = radius < 3 ? radius : 3;
+    cfg.min_cos = minCosine;
+    cfg.reserved = 0;
+    std::vector<cvs_chain_join> joins(2 * chains.size());
+    if ((rc = cvs_chain_joins(h, pts.data(), (int)np, tab.data(), (int)chains.size(), xy.data(), &cfg, joins.data(), CVS_MEM_HOST)) != CVS_OK)
+        return rc;
+    partners.assign(joins.size(), -1);
+    if (cosines) cosines->assign(joins.size(), std::numeric_limits<float>::quiet_NaN());
+    int count = 0;
+    for (size_t e = 0; e < joins.size(); ++e) {
+        const cvs_chain_join& j = joins[e];
+        if (!(j.flags & CVS_JOIN_MUTUAL)) continue;
+        partners[e] = j.partner;
+        if (cosines) (*cosines)[e] = j.cos;
+        if ((size_t)j.partner > e) ++count;   // each pair once
     }
     *n = count;
     return CVS_OK;
@@ -562,6 +611,14 @@ int SteerableFiltersG2::cornerContours(const Mat1f& response, const std::vector<
     return n;
 }
 
+int SteerableFiltersG2::joinContours(const Mat1f& response, const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags,
+                                     int radius, float minCosine, std::vector<int>& partners, std::vector<float>* cosines)
+{
+    int n = 0;
+    check(join_contours(m_handle, response, chains, flags, radius, minCosine, partners, cosines, &n), "cvs_chain_joins");
+    return n;
+}
+
 void SteerableFiltersG2::phaseWeights(const Mat1f& phase, Mat1f& lambda, float phi, bool signum, float k)
 {
     std::lock_guard<std::mutex> lock(g_static_mutex);
@@ -737,6 +794,14 @@ int SteerableFiltersG4::cornerContours(const Mat1f& response, const std::vector<
 {
     int n = 0;
     check(corner_contours(m_handle, response, chains, flags, radius, maxCosine, corners, cosines, &n), "cvs_chain_turns");
+    return n;
+}
+
+int SteerableFiltersG4::joinContours(const Mat1f& response, const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags,
+                                     int radius, float minCosine, std::vector<int>& partners, std::vector<float>* cosines)
+{
+    int n = 0;
+    check(join_contours(m_handle, response, chains, flags, radius, minCosine, partners, cosines, &n), "cvs_chain_joins");
     return n;
 }
 

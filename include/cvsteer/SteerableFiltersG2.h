@@ -99,6 +99,13 @@ public:
     // (optional): cosines[c] = the cosine of the turn at each of them.  flags as in approxContours.  Returns the number of corners
     int cornerContours(const Mat1f& response, const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags, int radius,
                        float maxCosine, std::vector<std::vector<int> >& corners, std::vector<std::vector<float> >* cosines = 0);
+    // contour joins (extension, cvs_chain_joins): which chains continue each other through a junction -- refineContours on `response`,
+    // then the joins of the chain ends by the contract of include/cvsteer_hip.h with min_arm = min(3, radius) and min_cos = minCosine.
+    // partners[2c] / partners[2c + 1] = the chain end (2 * chain + side, side 0 the head, 1 the tail) that the head / the tail of chains[c]
+    // continues into where the join is MUTUAL, else -1; cosines (optional): the cosine of the turn there, NaN where partners is -1.
+    // flags as in approxContours.  Returns the number of mutual joins, each pair of ends counted once
+    int joinContours(const Mat1f& response, const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags, int radius,
+                     float minCosine, std::vector<int>& partners, std::vector<float>* cosines = 0);
 
 protected:
     // the reference's protected members, same names (SteerableFiltersG2.h:62-66).  m_g1..m_h4 are the 7 tap vectors; the

@@ -55,6 +55,10 @@ public:
     // the object has no orientation state)
     int cornerContours(const Mat1f& response, const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags, int radius,
                        float maxCosine, std::vector<std::vector<int> >& corners, std::vector<std::vector<float> >* cosines = 0);
+    // addition: the joins of the chain ends, as in SteerableFiltersG2 (cvs_chain_joins; it refines on the object's own theta and throws
+    // where the object has no orientation state)
+    int joinContours(const Mat1f& response, const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags, int radius,
+                     float minCosine, std::vector<int>& partners, std::vector<float>* cosines = 0);
 
 protected:
     // the reference's protected members, same names (SteerableFiltersG4.h:50-56): 11 tap vectors; the planes m_g4a..m_h4f

@@ -679,6 +679,81 @@ int cvs_chain_turns(cvs_handle h, const int32_t* points, int n_points, const cvs
                     cvs_turn_summary* summary,  /* NULL, or n_chains records */
                     int mem);
 
+/* EXTENSION: contour joins -- what cvs_contour_chains took away when it cut the contours at their junctions: table[2c] and table[2c+1]
+ * say which other chain ends lie at the same node as the head and the tail of chain c, and which of them continues the chain most nearly
+ * straight.  One fixed-size record per chain END, so the table lines up with `chains`: no count, no prefix sum, nothing read back.  Needs
+ * no image size (any handle, before or after a setup).  Stitching chains into paths over the joins is left to the caller.
+ * ENDS.  Chain c = (S, L, F, R) = chains[c].  Its head, end 2c, sits at position j = S and its arm runs forwards (sign +1); its tail, end
+ * 2c+1, sits at j = S+L-1 and its arm runs backwards (sign -1).  A chain with CVS_CHAIN_CLOSED or with L < 2 has no ends: both its
+ * records are node = next = partner = -1, degree = n = 0, cos = sin = NaN, flags = CVS_JOIN_NONE.  Every NaN the call stores is the quiet
+ * NaN 0x7FC00000.
+ * NODE.  The key of an end is (R, y, x) of its INTEGER point, whether xy is given or not.  R is the fourth word of the entry -- 0 from
+ * cvs_contour_chains, the plane from cvs_contour_chains_batch -- and it IS READ here, unlike in cvs_polyline_segments and cvs_chain_turns:
+ * ends of different planes never share a node, so a batch table goes through as it is.  Ends with equal keys are at the same node.  node =
+ * the smallest end number at the node, degree = the number of ends there (this one included), next = the next larger end number there,
+ * wrapping from the largest to the smallest (its own number when degree is 1): following next visits the node's ends in a ring.  A loop
+ * that leaves and re-enters a junction has both its ends at one node; they may be partners.  degree > 8: CVS_JOIN_CROWDED on every end of
+ * the node -- node and degree are right, n and the arm's own flags are as computed, next = partner = -1, cos = sin = NaN.  (Never on a
+ * table of cvs_contour_chains: a pixel has at most 4 links, so degree <= 4 there, and never exactly 2.)
+ * ARM.  The arm of cvs_chain_turns at a chain end: n = min(radius, L-1) points; term k = (x[j +- k] - x[j], y[j +- k] - y[j]), k = 1 .. n,
+ * where the coordinates of a point are its (xs, ys) pair of `xy` widened to double when xy != NULL, else its integer point.  All
+ * arithmetic is IEEE double, every operation rounded on its own (no contraction): the terms are added in ascending k, starting from term
+ * 1, x and y separately; a = sum / (double)n (component by component, correctly rounded); len = sqrt(a.x*a.x + a.y*a.y) (correctly
+ * rounded).  CVS_JOIN_SHORT iff n < min_arm.  CVS_JOIN_DEGENERATE iff !(len > 0) or len is not finite (an arm centroid on the end itself,
+ * a NaN or an infinity in xy).  An end is ELIGIBLE iff none of NONE, CROWDED, SHORT, DEGENERATE and NO_CHAIN (below) is set.
+ * PAIR.  For eligible ends e != f at one node, with lo = min(e, f), hi = max(e, f): den = len_lo*len_hi; dt = -(a_lo.x*a_hi.x +
+ * a_lo.y*a_hi.y); cr = a_lo.y*a_hi.x - a_lo.x*a_hi.y.  cos(e,f) = (float)(dt/den) in both directions; sin(lo,hi) = (float)(cr/den) and
+ * sin(hi,lo) = sin(lo,hi) with its sign bit flipped.  Nothing is clamped (|cos| may exceed 1 by a rounding); from float coordinates den
+ * neither overflows nor underflows, so the cos and sin of an eligible pair are finite.  They are the turn of cvs_chain_turns with the
+ * arriving direction -a_e and the leaving direction a_f: cos = 1 is a straight continuation, sin > 0 a CLOCKWISE turn on the screen (y
+ * grows downwards).  So cos(e,f) and cos(f,e) are the same bits and sin(e,f), sin(f,e) differ in the sign bit alone, zeros included --
+ * the pair is evaluated once, from its smaller end, because cr taken from the larger end would be +0 again wherever the two products
+ * are equal (every straight diagonal continuation).
+ * PARTNER.  partner(e) = the eligible f != e at e's node with the largest cos(e,f), a float comparison: candidates are visited in
+ * ascending f and replace the one held only on strictly greater, so the smallest f wins a tie and +0 ties with -0.  cos and sin are
+ * those of (e, partner).  No candidate: partner = -1, cos = sin = NaN.  An end that is not eligible has partner -1 and NaN, and is
+ * nobody's partner.  CVS_JOIN_MUTUAL iff partner(partner(e)) == e and cos >= min_cos (float comparison).  MUTUAL joins pair ends off:
+ * partner is an involution on the ends that carry the flag, so following MUTUAL joins from any end never branches.
+ * TABLES.  As in cvs_chain_turns: HOST tables are checked in full -- CVS_E_BADARG unless the starts are the running sum of the lengths
+ * from 0 to n_points and every length is >= 1.  DEVICE tables are trusted for their meaning only: an entry that fails S >= 0, L >= 1,
+ * S + L <= n_points gets the records of a chain without ends with CVS_JOIN_NO_CHAIN added (flags = NONE | NO_CHAIN) and enters no node;
+ * nothing else is asked of the table (entries may overlap or leave gaps).  So no load and no store leaves the arrays; coordinates are
+ * never used as addresses.
+ * points, chains, xy and table are all in host or all in device memory (mem).  Device arrays: three launches, one lane per end in each
+ * -- the arms, the grouping of the ends by key in a hash table, the records -- queued on the handle's stream, nothing read back, nothing
+ * synchronised, capturable; the launch sequence depends on n_chains alone.  The result is a function of the inputs alone: the same call
+ * twice gives the same bytes (which slot of the hash table a node gets depends on a race; no output does).  Integer atomics only; no
+ * floating-point atomic is used.  The grouping needs handle scratch (grown only, freed by cvs_destroy): 112 bytes per chain and 16 bytes
+ * per slot of a table of max(8, the power of two >= 4 n_chains) slots -- at most 240 bytes per chain.  A call that would have to GROW the
+ * scratch while the stream is being captured returns CVS_E_UNSUPPORTED ("call once eagerly first", the rule of cvs_link); the handle works
+ * on.  Host arrays are staged in the same scratch, the call synchronises, and it returns CVS_E_UNSUPPORTED while the stream is being
+ * captured.  n_chains == 0: CVS_OK, nothing queued and nothing written.
+ * CVS_E_BADARG, nothing written: cfg NULL, radius outside 1 .. 64, min_arm outside 1 .. radius, min_cos NaN or outside -1 .. 1, reserved
+ * != 0; a negative count; a required array missing (points with n_points > 0, chains / table with n_chains > 0); n_points > 0 with
+ * n_chains == 0; an invalid mem; a pointer not aligned to 4 bytes; table overlapping an input; a HOST table as above.  n_points > 2^30 or
+ * n_chains > 2^26: CVS_E_SIZE. */
+typedef struct cvs_join_cfg {
+    int32_t radius;    /* 1..64: points per arm */
+    int32_t min_arm;   /* 1..radius: an end with a shorter arm joins nothing and is nobody's partner */
+    float   min_cos;   /* -1..1, NaN refused: CVS_JOIN_MUTUAL needs cos >= min_cos */
+    int32_t reserved;  /* 0 */
+} cvs_join_cfg;
+typedef struct cvs_chain_join {      /* 32 bytes, one per chain END: record 2c = head of chain c, 2c+1 = tail */
+    int32_t node;                    /* the smallest end number at the same node; -1: the end does not exist */
+    int32_t degree;                  /* ends at the node, this one included */
+    int32_t next;                    /* the next larger end at the node, cyclically (== own number when degree 1); -1 */
+    int32_t partner;                 /* the end that continues this one most nearly straight; -1 */
+    int32_t flags;                   /* CVS_JOIN_MUTUAL = 1, _NONE = 2, _CROWDED = 4, _SHORT = 8, _DEGENERATE = 16, _NO_CHAIN = 32 */
+    int32_t n;                       /* points of the arm */
+    float   cos, sin;                /* of the turn from arriving through this end to leaving through `partner`; NaN without partner */
+} cvs_chain_join;
+enum { CVS_JOIN_MUTUAL = 1, CVS_JOIN_NONE = 2, CVS_JOIN_CROWDED = 4, CVS_JOIN_SHORT = 8, CVS_JOIN_DEGENERATE = 16, CVS_JOIN_NO_CHAIN = 32 };
+int cvs_chain_joins(cvs_handle h, const int32_t* points, int n_points, const cvs_chain* chains, int n_chains,
+                    const float* xy,            /* NULL: the integer points */
+                    const cvs_join_cfg* cfg,
+                    cvs_chain_join* table,      /* 2 * n_chains records */
+                    int mem);
+
 /* ---- EXTENSION beyond the reference: the contour chain on the batch axis -- cvs_link, cvs_nonmax_batch, cvs_contours_batch ----
  * None of the three reads anything back: with device planes they queue a launch sequence that depends on the image size, the number of
  * planes and how the planes lie in memory (one constant stride, or not) -- never on what the planes hold -- and return. */
