@@ -803,6 +803,37 @@ class _CallerPipeline:
             xy, strength = torch.from_numpy(xy), torch.from_numpy(strength)
         return xy, strength
 
+    def _table_call(self, name, arrays, held, tables, args, out, out_text):
+        """What chain_measures, polyline_segments, chain_turns and chain_joins share around their C call `name`.  arrays: (label, array,
+        dtype, width) in the order they are converted, points first -- where the points are decides the path (Torch CUDA: the device
+        path); held: (labels, of, text) -- the arrays that hold one entry per entry of array `of`, and the ValueError if one does not;
+        tables: (record dtype, rows(count)) of every table the call writes, count[label] being the entries of an array; out: None, or
+        the caller's own uint8 CUDA tensor (a sequence of them for several tables), else ValueError(out_text); args(ptr, count, tab):
+        the C arguments between the handle and `mem`.  Returns `out` if given, else the list of tables as structured numpy arrays."""
+        dev = _is_torch(arrays[0][1]) and arrays[0][1].is_cuda
+        a = {label: self._chain_array(x, dev, dtype_np, width, label) for label, x, dtype_np, width in arrays}
+        count = {label: int(x.shape[0]) for label, x in a.items() if x is not None}
+        for labels, of, text in held:
+            if any(a[l] is not None and a[l].shape[0] != count[of] for l in labels):
+                raise ValueError(text)
+        shapes = [(rows(count), dt.itemsize) for dt, rows in tables]
+        if out is not None:
+            tabs = [out] if len(tables) == 1 else list(out)
+            if not (dev and len(tabs) == len(tables) and all(self._is_out(t, dev, np.uint8, sh) for t, sh in zip(tabs, shapes))):
+                raise ValueError(out_text)
+        elif dev:
+            tabs = [torch.empty(sh, dtype=torch.uint8, device=a[arrays[0][0]].device) for sh in shapes]
+        else:
+            tabs = [np.zeros(sh[0], dt) for (dt, _), sh in zip(tables, shapes)]
+        if dev:
+            self._bind_stream(a[arrays[0][0]])
+        ptr = {label: self._array_ptr(x) for label, x in a.items()}
+        self._check(getattr(lib(), name)(self._h, *args(ptr, count, [self._array_ptr(t) for t in tabs]), L.MEM_DEVICE if dev else L.MEM_HOST),
+                    name)
+        if out is not None:
+            return out
+        return [t.cpu().numpy().view(dt).reshape(sh[0]) for t, (dt, _), sh in zip(tabs, tables, shapes)] if dev else tabs
+
     def chain_measures(self, points, chains, strength=None, xy=None, out=None):
         """One record per chain (cvs_chain_measures): a numpy structured array with the fields of `cvs_chain_measure` (axial, diagonal,
         other: steps by kind; peak_index, peak, weakest, sum of `strength`; length: the Euclidean length, of the sub-pixel `xy` when
@@ -810,31 +841,14 @@ class _CallerPipeline:
         and xy (N, 2) float32 as chain_refine returns them.  Torch CUDA arrays take the device path: the table is written on the device
         and downloaded for the return value -- or, with out= an (M, 40) uint8 CUDA tensor, left there (nothing read back, capturable;
         out.cpu().numpy().view(MEASURE_DTYPE) reads it) and `out` is returned."""
-        dev = _is_torch(points) and points.is_cuda
-        points = self._chain_array(points, dev, np.int32, 2, "points")
-        chains = self._chain_array(chains, dev, np.int32, 4, "chains")
-        strength = self._chain_array(strength, dev, np.float32, 0, "strength")
-        xy = self._chain_array(xy, dev, np.float32, 2, "xy")
-        n, m = int(points.shape[0]), int(chains.shape[0])
-        if (strength is not None and strength.shape[0] != n) or (xy is not None and xy.shape[0] != n):
-            raise ValueError("strength and xy: one entry per point")
         size = self.MEASURE_DTYPE.itemsize
-        if out is not None:
-            if not (dev and self._is_out(out, dev, np.uint8, (m, size))):
-                raise ValueError("out: a contiguous (M, %d) uint8 CUDA tensor, with device arrays" % size)
-            table = out
-        elif dev:
-            table = torch.empty((m, size), dtype=torch.uint8, device=points.device)
-        else:
-            table = np.zeros(m, self.MEASURE_DTYPE)
-        if dev:
-            self._bind_stream(points)
-        self._check(lib().cvs_chain_measures(self._h, self._array_ptr(points), n, self._array_ptr(chains), m, self._array_ptr(xy),
-                                             self._array_ptr(strength), self._array_ptr(table), L.MEM_DEVICE if dev else L.MEM_HOST),
-                    "cvs_chain_measures")
-        if out is not None or not dev:
-            return table
-        return table.cpu().numpy().view(self.MEASURE_DTYPE).reshape(m)
+        r = self._table_call(
+            "cvs_chain_measures",
+            [("points", points, np.int32, 2), ("chains", chains, np.int32, 4), ("strength", strength, np.float32, 0), ("xy", xy, np.float32, 2)],
+            [(("strength", "xy"), "points", "strength and xy: one entry per point")], [(self.MEASURE_DTYPE, lambda c: c["chains"])],
+            lambda p, c, t: (p["points"], c["points"], p["chains"], c["chains"], p["xy"], p["strength"], t[0]),
+            out, "out: a contiguous (M, %d) uint8 CUDA tensor, with device arrays" % size)
+        return r if out is not None else r[0]
 
     def contour_edgels(self, mask, map, theta=None):
         """contour_chains(mask), chain_refine on the un-thinned `map` the mask came from, chain_measures on both: the linked contours of
@@ -857,35 +871,17 @@ class _CallerPipeline:
         Torch CUDA arrays take the device path: the table is written on the device and downloaded for the return value -- or, with out= a
         (V, 128) uint8 CUDA tensor, left there (two launches, nothing read back, capturable; out.cpu().numpy().view(SEGMENT_DTYPE) reads
         it) and `out` is returned.  numpy arrays and torch CPU tensors take the host path.  include/cvsteer_hip.h has the contract."""
-        dev = _is_torch(points) and points.is_cuda
-        points = self._chain_array(points, dev, np.int32, 2, "points")
-        chains = self._chain_array(chains, dev, np.int32, 4, "chains")
-        polylines = self._chain_array(polylines, dev, np.int32, 4, "polylines")
-        index = self._chain_array(index, dev, np.int32, 0, "index")
-        xy = self._chain_array(xy, dev, np.float32, 2, "xy")
-        strength = self._chain_array(strength, dev, np.float32, 0, "strength")
-        n, m, v = int(points.shape[0]), int(chains.shape[0]), int(index.shape[0])
-        if polylines.shape[0] != m:
-            raise ValueError("polylines: one entry per chain")
-        if (strength is not None and strength.shape[0] != n) or (xy is not None and xy.shape[0] != n):
-            raise ValueError("strength and xy: one entry per point")
         size = self.SEGMENT_DTYPE.itemsize
-        if out is not None:
-            if not (dev and self._is_out(out, dev, np.uint8, (v, size))):
-                raise ValueError("out: a contiguous (V, %d) uint8 CUDA tensor, with device arrays" % size)
-            table = out
-        elif dev:
-            table = torch.empty((v, size), dtype=torch.uint8, device=points.device)
-        else:
-            table = np.zeros(v, self.SEGMENT_DTYPE)
-        if dev:
-            self._bind_stream(points)
-        self._check(lib().cvs_polyline_segments(self._h, self._array_ptr(points), n, self._array_ptr(chains), self._array_ptr(polylines), m,
-                                                self._array_ptr(index), v, self._array_ptr(xy), self._array_ptr(strength),
-                                                self._array_ptr(table), L.MEM_DEVICE if dev else L.MEM_HOST), "cvs_polyline_segments")
-        if out is not None or not dev:
-            return table
-        return table.cpu().numpy().view(self.SEGMENT_DTYPE).reshape(v)
+        r = self._table_call(
+            "cvs_polyline_segments",
+            [("points", points, np.int32, 2), ("chains", chains, np.int32, 4), ("polylines", polylines, np.int32, 4),
+             ("index", index, np.int32, 0), ("xy", xy, np.float32, 2), ("strength", strength, np.float32, 0)],
+            [(("polylines",), "chains", "polylines: one entry per chain"), (("strength", "xy"), "points", "strength and xy: one entry per point")],
+            [(self.SEGMENT_DTYPE, lambda c: c["index"])],
+            lambda p, c, t: (p["points"], c["points"], p["chains"], p["polylines"], c["chains"], p["index"], c["index"], p["xy"], p["strength"],
+                             t[0]),
+            out, "out: a contiguous (V, %d) uint8 CUDA tensor, with device arrays" % size)
+        return r if out is not None else r[0]
 
     def contour_segments(self, mask, map, eps, theta=None, weighted=False, min_points=2):
         """The straight segments of the linked contours of a mask, to sub-pixel accuracy: contour_chains(mask) ->
@@ -919,37 +915,15 @@ class _CallerPipeline:
         and downloaded for the return value -- or, with out= an (N, 32) uint8 CUDA tensor (summary=True: a pair with an (M, 16) one), left
         there (two or three launches, nothing read back, capturable; out.cpu().numpy().view(TURN_DTYPE) reads it) and `out` is returned.
         numpy arrays and torch CPU tensors take the host path.  include/cvsteer_hip.h has the contract."""
-        dev = _is_torch(points) and points.is_cuda
-        points = self._chain_array(points, dev, np.int32, 2, "points")
-        chains = self._chain_array(chains, dev, np.int32, 4, "chains")
-        xy = self._chain_array(xy, dev, np.float32, 2, "xy")
-        n, m = int(points.shape[0]), int(chains.shape[0])
-        if xy is not None and xy.shape[0] != n:
-            raise ValueError("xy: one entry per point")
-        cfg = L.TurnCfg(int(radius), int(radius if min_arm is None else min_arm), int(radius if nms is None else nms), float(max_cos))
         size, ssize = self.TURN_DTYPE.itemsize, self.TURN_SUMMARY_DTYPE.itemsize
-        sums = None
-        if out is not None:
-            table, sums = out if summary else (out, None)
-            if not (dev and self._is_out(table, dev, np.uint8, (n, size)) and (not summary or self._is_out(sums, dev, np.uint8, (m, ssize)))):
-                raise ValueError("out: a contiguous (N, %d) uint8 CUDA tensor%s, with device arrays"
-                                 % (size, " and an (M, %d) one" % ssize if summary else ""))
-        elif dev:
-            table = torch.empty((n, size), dtype=torch.uint8, device=points.device)
-            sums = torch.empty((m, ssize), dtype=torch.uint8, device=points.device) if summary else None
-        else:
-            table = np.zeros(n, self.TURN_DTYPE)
-            sums = np.zeros(m, self.TURN_SUMMARY_DTYPE) if summary else None
-        if dev:
-            self._bind_stream(points)
-        self._check(lib().cvs_chain_turns(self._h, self._array_ptr(points), n, self._array_ptr(chains), m, self._array_ptr(xy), C.byref(cfg),
-                                          self._array_ptr(table), self._array_ptr(sums), L.MEM_DEVICE if dev else L.MEM_HOST), "cvs_chain_turns")
-        if out is not None:
-            return out
-        if dev:
-            table = table.cpu().numpy().view(self.TURN_DTYPE).reshape(n)
-            sums = sums.cpu().numpy().view(self.TURN_SUMMARY_DTYPE).reshape(m) if summary else None
-        return (table, sums) if summary else table
+        cfg = lambda: L.TurnCfg(int(radius), int(radius if min_arm is None else min_arm), int(radius if nms is None else nms), float(max_cos))
+        r = self._table_call(
+            "cvs_chain_turns", [("points", points, np.int32, 2), ("chains", chains, np.int32, 4), ("xy", xy, np.float32, 2)],
+            [(("xy",), "points", "xy: one entry per point")],
+            [(self.TURN_DTYPE, lambda c: c["points"])] + ([(self.TURN_SUMMARY_DTYPE, lambda c: c["chains"])] if summary else []),
+            lambda p, c, t: (p["points"], c["points"], p["chains"], c["chains"], p["xy"], C.byref(cfg()), t[0], t[1] if summary else None),
+            out, "out: a contiguous (N, %d) uint8 CUDA tensor%s, with device arrays" % (size, " and an (M, %d) one" % ssize if summary else ""))
+        return r if out is not None else tuple(r) if summary else r[0]
 
     def contour_corners(self, mask, map, theta=None, **cfg):
         """The corners of the linked contours of a mask: contour_chains(mask) -> chain_refine on the un-thinned `map` the mask came from ->
@@ -978,30 +952,14 @@ class _CallerPipeline:
         the device and downloaded for the return value -- or, with out= a (2M, 32) uint8 CUDA tensor, left there (three launches, nothing
         read back, capturable once the handle's scratch has its size; out.cpu().numpy().view(JOIN_DTYPE) reads it) and `out` is returned.
         numpy arrays and torch CPU tensors take the host path.  include/cvsteer_hip.h has the contract."""
-        dev = _is_torch(points) and points.is_cuda
-        points = self._chain_array(points, dev, np.int32, 2, "points")
-        chains = self._chain_array(chains, dev, np.int32, 4, "chains")
-        xy = self._chain_array(xy, dev, np.float32, 2, "xy")
-        n, m = int(points.shape[0]), int(chains.shape[0])
-        if xy is not None and xy.shape[0] != n:
-            raise ValueError("xy: one entry per point")
-        cfg = L.JoinCfg(int(radius), int(min(3, radius) if min_arm is None else min_arm), float(min_cos), 0)
         size = self.JOIN_DTYPE.itemsize
-        if out is not None:
-            if not (dev and self._is_out(out, dev, np.uint8, (2 * m, size))):
-                raise ValueError("out: a contiguous (2 M, %d) uint8 CUDA tensor, with device arrays" % size)
-            table = out
-        elif dev:
-            table = torch.empty((2 * m, size), dtype=torch.uint8, device=points.device)
-        else:
-            table = np.zeros(2 * m, self.JOIN_DTYPE)
-        if dev:
-            self._bind_stream(points)
-        self._check(lib().cvs_chain_joins(self._h, self._array_ptr(points), n, self._array_ptr(chains), m, self._array_ptr(xy), C.byref(cfg),
-                                          self._array_ptr(table), L.MEM_DEVICE if dev else L.MEM_HOST), "cvs_chain_joins")
-        if out is not None or not dev:
-            return table
-        return table.cpu().numpy().view(self.JOIN_DTYPE).reshape(2 * m)
+        cfg = lambda: L.JoinCfg(int(radius), int(min(3, radius) if min_arm is None else min_arm), float(min_cos), 0)
+        r = self._table_call(
+            "cvs_chain_joins", [("points", points, np.int32, 2), ("chains", chains, np.int32, 4), ("xy", xy, np.float32, 2)],
+            [(("xy",), "points", "xy: one entry per point")], [(self.JOIN_DTYPE, lambda c: 2 * c["chains"])],
+            lambda p, c, t: (p["points"], c["points"], p["chains"], c["chains"], p["xy"], C.byref(cfg()), t[0]),
+            out, "out: a contiguous (2 M, %d) uint8 CUDA tensor, with device arrays" % size)
+        return r if out is not None else r[0]
 
     def contour_joins(self, mask, map, theta=None, **cfg):
         """The joins of the linked contours of a mask: contour_chains(mask) -> chain_refine on the un-thinned `map` the mask came from ->

@@ -27,20 +27,6 @@ int ceil_log2(int n)
     return r;
 }
 
-bool misaligned(const void* p) { return reinterpret_cast<uintptr_t>(p) % alignof(int32_t) != 0; }
-
-// an array of `n` records of `words` 4-byte words as a plane, for the overlap rule of the contour tail (check_disjoint)
-cvs_plane array_plane(const void* p, long long n, int words, int mem)
-{
-    cvs_plane q{};
-    q.data = (p && n > 0) ? const_cast<float*>(static_cast<const float*>(p)) : nullptr;
-    q.rows = (int)n;
-    q.cols = words;
-    q.step = (size_t)words * 4;
-    q.mem = mem;
-    return q;
-}
-
 // planes at one stride (an [N, H, W] block, the staged copies of host planes, the state blocks of a batch) are addressed arithmetically;
 // anything else through the device table at `tab`, which launches fill from their arguments
 int plane_set(cvs_handle h, const std::vector<MaskRef>& d, MaskRef* tab, PlaneSet& out)
@@ -269,22 +255,12 @@ int cvs_chain_refine_batch(cvs_handle h, int frames, int n_maps, const cvs_plane
     a.n = n;
     a.n_maps = n_maps;
     a.n_points = n_points;
-    a.points = points;
-    a.ranges = ranges;
-    a.xy = xy;
-    a.strength = strength;
-    if (host) {
-        Scratch sc;
-        const size_t o_pts = sc.reserve((size_t)n_points * 8), o_xy = sc.reserve((size_t)n_points * 8), o_str = sc.reserve((size_t)n_points * 4);
-        const size_t o_rng = sc.reserve(((size_t)n + 1) * 8);
-        if ((rc = grow_scratch(h, "hipMalloc(&h->ch_scr, need)", h->ch_scr, h->ch_scr_bytes, sc.need, 1))) return rc;
-        HIP_TRY(h, hipMemcpyAsync(h->ch_scr + o_pts, points, (size_t)n_points * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(h, hipMemcpyAsync(h->ch_scr + o_rng, ranges, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, s));
-        a.points = reinterpret_cast<const int32_t*>(h->ch_scr + o_pts);
-        a.ranges = reinterpret_cast<const int32_t*>(h->ch_scr + o_rng);
-        a.xy = reinterpret_cast<float*>(h->ch_scr + o_xy);
-        a.strength = strength ? reinterpret_cast<float*>(h->ch_scr + o_str) : nullptr;
-    }
+    Staged st(h, "cvs_chain_refine_batch", host);   // (the arrays; the planes go through the arena)
+    st.in(a.points, points, (size_t)n_points * 8);
+    st.in(a.ranges, ranges, ((size_t)n + 1) * 8);
+    st.out(a.xy, xy, (size_t)n_points * 8);
+    st.out(a.strength, strength, (size_t)n_points * 4);
+    if ((rc = st.commit()) || (rc = st.upload(s))) return rc;
     MaskRef* tab = need_tab ? reinterpret_cast<MaskRef*>(arena_take(h, tab_elems)) : nullptr;
     for (int k = 0; k < n + frames; ++k) {
         PlaneRef r;
@@ -293,10 +269,7 @@ int cvs_chain_refine_batch(cvs_handle h, int frames, int n_maps, const cvs_plane
     }
     if ((rc = plane_set(h, dm, tab, a.maps)) || (rc = plane_set(h, dt, tab + n, a.theta))) return rc;
     HIP_TRY(h, launch_chain_refine_batch(a, s));
-    if (host) {
-        HIP_TRY(h, hipMemcpyAsync(xy, a.xy, (size_t)n_points * 8, hipMemcpyDeviceToHost, s));
-        if (strength) HIP_TRY(h, hipMemcpyAsync(strength, a.strength, (size_t)n_points * 4, hipMemcpyDeviceToHost, s));
-    }
+    if ((rc = st.download(s))) return rc;
     if (sync) HIP_TRY(h, hipStreamSynchronize(s));
     return CVS_OK;
 }

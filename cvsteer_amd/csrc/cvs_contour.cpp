@@ -5,6 +5,8 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
+#include <string>
 #include <vector>
 
 #include "cvs_contour.h"
@@ -76,6 +78,56 @@ int fetch_mask(Call& c, const cvs_plane* o, bool u8, const void* p, size_t pitch
 {
     if (!staged_bytes(o, u8)) return CVS_OK;
     HIP_TRY(c.h, copy_rows(o->data, o->step, p, pitch, (size_t)o->cols, o->rows, hipMemcpyDeviceToHost, c.h->stream));
+    return CVS_OK;
+}
+
+cvs_plane array_plane(const void* p, long long n, int words, int mem)
+{
+    cvs_plane q{};
+    q.data = n > 0 ? const_cast<float*>(static_cast<const float*>(p)) : nullptr;
+    q.rows = (int)n;
+    q.cols = words;
+    q.step = (size_t)words * 4;
+    q.mem = mem;
+    return q;
+}
+
+int Staged::commit()
+{
+    if (n_ == 0) return CVS_OK;
+    if (sc_.need > h_->ch_scr_bytes) {
+        bool cap = false;
+        if (const int rc = capturing(h_, cap)) return rc;
+        if (cap)
+            return fail(h_, CVS_E_UNSUPPORTED,
+                        (std::string(call_) + " would have to grow the handle's scratch during capture: call once eagerly first").c_str());
+    }
+    if (const int rc = grow_scratch(h_, "hipMalloc(&h->ch_scr, need)", h_->ch_scr, h_->ch_scr_bytes, sc_.need, 1)) return rc;
+    for (int i = 0; i < n_; ++i) {
+        unsigned char* p = h_->ch_scr + items_[i].off;
+        std::memcpy(items_[i].field, &p, sizeof(p));   // (the field is an object pointer of some type: all of one representation)
+    }
+    return CVS_OK;
+}
+
+int Staged::copy(hipStream_t s, Dir dir)
+{
+    for (int i = 0; i < n_; ++i) {
+        const Item& t = items_[i];
+        if (t.dir != dir || t.bytes == 0) continue;
+        if (dir == kUp) HIP_TRY(h_, hipMemcpyAsync(h_->ch_scr + t.off, t.host, t.bytes, hipMemcpyHostToDevice, s));
+        else HIP_TRY(h_, hipMemcpyAsync(t.host, h_->ch_scr + t.off, t.bytes, hipMemcpyDeviceToHost, s));
+    }
+    return CVS_OK;
+}
+
+int Staged::upload(hipStream_t s) { return copy(s, kUp); }
+int Staged::download(hipStream_t s) { return copy(s, kDown); }
+
+int Staged::fetch(hipStream_t s)
+{
+    if (const int rc = download(s)) return rc;
+    if (host_) HIP_TRY(h_, hipStreamSynchronize(s));
     return CVS_OK;
 }
 

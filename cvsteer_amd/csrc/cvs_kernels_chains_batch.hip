@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include "cvs_cc_device.h"
+#include "cvs_chain_device.h"
 #include "cvs_chains_batch.h"
 #include "cvs_device_math.h"
 
@@ -316,13 +317,6 @@ __global__ __launch_bounds__(256) void k_chb_ranges(const int32_t* chains, int n
 // so the search reads inside the table and ends on a plane that exists whatever the table holds.  Behind it: k_chain_refine
 // (cvs_kernels_refine.hip), operation for operation.
 // ---------------------------------------------------------------------------------------
-struct IntPair {
-    int x, y;
-};
-struct FloatPair {
-    float x, y;
-};
-
 __global__ __launch_bounds__(256) void k_chain_refine_batch(const RefineBatchArgs a)
 {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;

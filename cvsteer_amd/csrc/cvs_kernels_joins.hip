@@ -2,7 +2,7 @@
 // which (cvs_chain_joins), one record per chain end, for gfx950.
 //
 // One lane per END in all three launches; ends are few beside points (two per chain), so nothing here is tuned for bandwidth.
-// k_join_arms: the lane reads its chain's entry, checks it before it is used as an address (jn_entry), adds the terms of its arm in
+// k_join_arms: the lane reads its chain's entry, checks it before it is used as an address (chain_entry), adds the terms of its arm in
 // ascending k -- sequential in the lane, so the arm is a function of the inputs, bit for bit -- and leaves arm, key (plane, y, x of the
 // integer point) and flags in its JnEnd.  The launch also clears the hash table of the nodes, at most four slots per lane.
 // k_join_insert: every end that exists looks for the slot of its node by open addressing from the hash of its key.  An empty slot is
@@ -22,6 +22,7 @@
 
 #include <climits>
 
+#include "cvs_chain_device.h"
 #include "cvs_joins.h"
 
 namespace cvs {
@@ -30,10 +31,6 @@ namespace {
 
 constexpr int kJnBlock = 256;   // ends per workgroup
 static_assert(2ll * kJoinMaxChains / kJnBlock <= (long long)kGridMaxX, "one workgroup per 256 ends never meets the grid bound");
-
-struct JnPair {   // a point as it lies in memory (4-byte aligned): an (x, y) int32 pair of `points`, or the bits of an (xs, ys) pair of `xy`
-    uint32_t x, y;
-};
 
 struct JnEnd {    // what launch 1 (arm, key, n, flags) and launch 2 (slot, link) leave of one end
     double ax, ay, len;   // the arm: the centroid of its points relative to the end, and its length
@@ -55,17 +52,6 @@ static_assert(sizeof(JnSlot) == kJoinSlotBytes, "JnSlot");
 
 __device__ __forceinline__ JnEnd* jn_ends(const JoinArgs& a) { return reinterpret_cast<JnEnd*>(a.scratch); }
 __device__ __forceinline__ JnSlot* jn_slots(const JoinArgs& a) { return reinterpret_cast<JnSlot*>(a.scratch + 2 * (size_t)a.n_chains * kJoinEndBytes); }
-
-// the entry of chain c, and whether it lies inside `points`
-__device__ __forceinline__ bool jn_entry(const JoinArgs& a, int c, int& S, int& L, int& F, int& R)
-{
-    const int32_t* e = a.chains + 4 * (size_t)c;
-    S = e[0];
-    L = e[1];
-    F = e[2];
-    R = e[3];
-    return S >= 0 && L >= 1 && (long long)S + L <= (long long)a.n_points;
-}
 
 __device__ __forceinline__ unsigned long long jn_hash(int x, int y, int r)
 {
@@ -162,8 +148,9 @@ __global__ __launch_bounds__(kJnBlock) void k_join_arms(const JoinArgs a)
     me.slot = me.link = -1;
     const int c = (int)(id >> 1);
     const bool tail = (id & 1) != 0;
-    int S, L, F, R;
-    if (!jn_entry(a, c, S, L, F, R)) {
+    const ChainEntry e = chain_entry(a.chains, c, a.n_points);
+    const int S = e.start, L = e.len, F = e.flags, R = e.plane;
+    if (!e.ok()) {
         me.flags = kJoinNone | kJoinNoChain;
     } else if ((F & kChainClosed) || L < 2) {
         me.flags = kJoinNone;
@@ -173,9 +160,9 @@ __global__ __launch_bounds__(kJnBlock) void k_join_arms(const JoinArgs a)
         const int sign = tail ? -1 : 1;
         const int n = min(a.radius, L - 1);
         const bool sub = a.xy != nullptr;
-        const JnPair* src = reinterpret_cast<const JnPair*>(sub ? static_cast<const void*>(a.xy) : static_cast<const void*>(a.points));
+        const WordPair* src = reinterpret_cast<const WordPair*>(sub ? static_cast<const void*>(a.xy) : static_cast<const void*>(a.points));
         auto coords = [&](long long p, double& x, double& y) {
-            const JnPair v = src[p];
+            const WordPair v = src[p];
             x = sub ? (double)__uint_as_float(v.x) : (double)(int)v.x;
             y = sub ? (double)__uint_as_float(v.y) : (double)(int)v.y;
         };

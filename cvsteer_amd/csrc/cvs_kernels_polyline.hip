@@ -17,21 +17,10 @@
 // empty chain, so no load or store leaves the arrays whatever a device table holds; coordinates are never used as addresses.
 #include <hip/hip_runtime.h>
 
+#include "cvs_chain_device.h"
 #include "cvs_polyline.h"
 
 namespace cvs {
-
-struct PlChain {
-    int start, len, flags;   // len == 0: an empty chain
-};
-
-__device__ __forceinline__ PlChain pl_chain(const int32_t* chains, long long c, int n_points)
-{
-    const int32_t* t = chains + 4 * c;
-    const int s = t[0], l = t[1], f = t[2];
-    const bool ok = s >= 0 && l >= 1 && (long long)s + l <= (long long)n_points;
-    return PlChain{ok ? s : 0, ok ? l : 0, f};
-}
 
 // v(i) of the split rule for the point (qx, qy) against the segment a -> b: |cross| for a != b, the squared distance from a otherwise.
 // For coordinates beyond the contract's range the products wrap instead of overflowing and the sign bit is dropped: a value is never negative,
@@ -128,7 +117,7 @@ __global__ __launch_bounds__(256) void k_pl_keep_wave(const int32_t* points, int
     const int lane = threadIdx.x & 63;
     const long long c = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (c >= n_chains) return;
-    const PlChain t = pl_chain(chains, c, n_points);
+    const ChainEntry t = chain_or_empty(chains, c, n_points);   // (a broken entry: an empty chain)
     if (t.len > kPlWaveMax) return;   // k_pl_keep_block's
     if (t.len == 0) {
         if (lane == 0) count[c] = 0;
@@ -176,34 +165,6 @@ __global__ __launch_bounds__(256) void k_pl_keep_wave(const int32_t* points, int
 }
 
 // ---------------------------------------------------------------------------------------
-// The long chains of a table, for the two workgroup kernels: a workgroup takes slices of 256 table entries (slice = blockIdx.x, + gridDim.x,
-// ...), ballots the entries that are longer than kPlWaveMax and calls f(chain index, chain) for each, all 256 lanes together.
-// lm: four words of LDS.
-// ---------------------------------------------------------------------------------------
-template <class F>
-__device__ __forceinline__ void pl_long_chains(const int32_t* chains, int n_chains, int n_points, unsigned long long* lm, F f)
-{
-    for (long long base = (long long)blockIdx.x * 256; base < n_chains; base += (long long)gridDim.x * 256) {
-        const long long c = base + threadIdx.x;
-        const bool is_long = c < n_chains && pl_chain(chains, c, n_points).len > kPlWaveMax;
-        const unsigned long long b = __ballot(is_long);
-        if ((threadIdx.x & 63) == 0) lm[threadIdx.x >> 6] = b;
-        __syncthreads();
-#pragma unroll 1
-        for (int w = 0; w < 4; ++w) {
-            unsigned long long bits = lm[w];
-            while (bits) {
-                const int k = __ffsll((long long)bits) - 1;
-                bits &= bits - 1;
-                const long long cc = base + w * 64 + k;
-                f(cc, pl_chain(chains, cc, n_points));
-            }
-        }
-        __syncthreads();   // lm is written again
-    }
-}
-
-// ---------------------------------------------------------------------------------------
 // Step 1, long chains.  The flags are the chain's own bytes of KEEP.  A split is marked by one lane and read again only behind a barrier (the
 // one in front of every search for the next kept point).  That search is done by every wave on its own, 64 flags at a time; the last point of
 // the virtual list counts as kept without being read, so the search ends whatever the bytes hold.
@@ -229,7 +190,7 @@ __global__ __launch_bounds__(256) void k_pl_keep_block(const int32_t* points, in
 {
     __shared__ unsigned long long lm[4];
     __shared__ PlBest best;
-    pl_long_chains(chains, n_chains, n_points, lm, [&](long long c, const PlChain& t) {
+    long_chains(chains, n_chains, n_points, kPlWaveMax, lm, [&](long long c, const ChainEntry& t) {
         const int tid = threadIdx.x, wave = tid >> 6;
         const int L = t.len, closed = t.flags & kChainClosed, last = L + closed - 1;   // last: index of the last point of the virtual list
         const int32_t* P = points + 2 * (size_t)t.start;
@@ -369,7 +330,7 @@ __global__ __launch_bounds__(256) void k_pl_emit_wave(const int32_t* points, int
     const int lane = threadIdx.x & 63;
     const long long c = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (c >= n_chains || (unsigned)partials[blocks] > (unsigned)capacity) return;
-    const PlChain t = pl_chain(chains, c, n_points);
+    const ChainEntry t = chain_or_empty(chains, c, n_points);   // (a broken entry: an empty chain)
     if (t.len == 0 || t.len > kPlWaveMax) return;
     const int32_t* P = points + 2 * (size_t)t.start;
     const uint8_t* K = keep + (size_t)t.start;
@@ -390,7 +351,7 @@ __global__ __launch_bounds__(256) void k_pl_emit_block(const int32_t* points, in
     __shared__ unsigned long long lm[4];
     __shared__ int wc[2][4];
     if ((unsigned)partials[blocks] > (unsigned)capacity) return;   // (the same for every lane of the launch)
-    pl_long_chains(chains, n_chains, n_points, lm, [&](long long c, const PlChain& t) {
+    long_chains(chains, n_chains, n_points, kPlWaveMax, lm, [&](long long c, const ChainEntry& t) {
         const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
         const int32_t* P = points + 2 * (size_t)t.start;
         const uint8_t* K = keep + (size_t)t.start;

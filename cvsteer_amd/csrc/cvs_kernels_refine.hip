@@ -12,18 +12,11 @@
 // Built with -ffp-contract=off: every product and sum below rounds on its own, as the contract in include/cvsteer_hip.h says.
 #include <hip/hip_runtime.h>
 
+#include "cvs_chain_device.h"
 #include "cvs_device_math.h"
 #include "cvs_refine.h"
 
 namespace cvs {
-
-// two 4-byte words that travel as one 8-byte access (the arrays are aligned to 4 bytes, which a global dwordx2 access allows)
-struct IntPair {
-    int x, y;
-};
-struct FloatPair {
-    float x, y;
-};
 
 __global__ __launch_bounds__(256) void k_chain_refine(const RefineArgs a)
 {
@@ -122,21 +115,9 @@ __device__ __forceinline__ void ms_wave_merge(MsAcc& a)
     }
 }
 
-struct MsChain {
-    int start, len, flags;   // len == 0: an empty chain
-};
-
-__device__ __forceinline__ MsChain ms_chain(const int32_t* chains, long long c, int n_points)
-{
-    const int32_t* t = chains + 4 * c;
-    const int s = t[0], l = t[1], f = t[2];
-    const bool ok = s >= 0 && l >= 1 && (long long)s + l <= (long long)n_points;
-    return MsChain{ok ? s : 0, ok ? l : 0, f};
-}
-
 // the points first, first + stride, ... of chain t and the steps that leave them (step i goes from point i to point i + 1, the closing step of
 // a closed chain from the last point to the first)
-__device__ __forceinline__ MsAcc ms_gather(const MeasureArgs& a, const MsChain& t, int first, int stride)
+__device__ __forceinline__ MsAcc ms_gather(const MeasureArgs& a, const ChainEntry& t, int first, int stride)
 {
     MsAcc acc = ms_zero();
     const int L = t.len, steps = L - 1 + ((t.flags & kChainClosed) ? 1 : 0);
@@ -175,7 +156,7 @@ __device__ __forceinline__ MsAcc ms_gather(const MeasureArgs& a, const MsChain& 
     return acc;
 }
 
-__device__ __forceinline__ void ms_store(uint32_t* table, long long c, const MsChain& t, const MsAcc& acc)
+__device__ __forceinline__ void ms_store(uint32_t* table, long long c, const ChainEntry& t, const MsAcc& acc)
 {
     uint32_t* r = table + (size_t)kMeasureWords * c;
     if (t.len == 0) {
@@ -202,27 +183,18 @@ __global__ __launch_bounds__(256) void k_measure_wave(const MeasureArgs a)
     const int lane = threadIdx.x & 63;
     const long long c = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (c >= a.n_chains) return;
-    const MsChain t = ms_chain(a.chains, c, a.n_points);
+    const ChainEntry t = chain_or_empty(a.chains, c, a.n_points);   // (a broken entry: an empty chain, the all-zero record)
     if (t.len > kPlWaveMax) return;   // k_measure_block's
     MsAcc acc = ms_gather(a, t, lane, 64);
     ms_wave_merge(acc);
     if (lane == 0) ms_store(a.table, c, t, acc);
 }
 
-// the long chains of a table (ms_long_entries, cvs_refine.h): f(chain index, chain) for each chain longer than kPlWaveMax
-template <class F>
-__device__ __forceinline__ void ms_long_chains(const int32_t* chains, int n_chains, int n_points, unsigned long long* lm, F f)
-{
-    ms_long_entries(
-        n_chains, lm, [&](long long c) { return ms_chain(chains, c, n_points).len > kPlWaveMax; },
-        [&](long long c) { f(c, ms_chain(chains, c, n_points)); });
-}
-
 __global__ __launch_bounds__(256) void k_measure_block(const MeasureArgs a)
 {
     __shared__ unsigned long long lm[4];
     __shared__ MsAcc part[4];
-    ms_long_chains(a.chains, a.n_chains, a.n_points, lm, [&](long long c, const MsChain& t) {
+    long_chains(a.chains, a.n_chains, a.n_points, kPlWaveMax, lm, [&](long long c, const ChainEntry& t) {
         const int tid = threadIdx.x;
         MsAcc acc = ms_gather(a, t, tid, 256);
         ms_wave_merge(acc);

@@ -16,6 +16,7 @@
 // the double divisions and square roots are the correctly rounded ones.
 #include <hip/hip_runtime.h>
 
+#include "cvs_chain_device.h"
 #include "cvs_segments.h"
 
 #ifndef CVS_SEG_GROUP
@@ -29,13 +30,6 @@ namespace {
 constexpr int kSgGroup = CVS_SEG_GROUP;   // lanes that share a span of at most kPlWaveMax points
 static_assert(kSgGroup == 16 || kSgGroup == 32 || kSgGroup == 64, "a power of two that divides a wave, and a shuffle width");
 
-struct SgInt2 {
-    int x, y;
-};
-struct SgFloat2 {
-    float x, y;
-};
-
 // the span that starts at a vertex.  count == 0: no span (first and chain are still the record's)
 struct SgSpan {
     int first, count, chain, flags;
@@ -45,18 +39,14 @@ struct SgSpan {
 __device__ __forceinline__ SgSpan sg_span(const SegmentArgs& a, long long k)
 {
     const int i0 = a.index[k];
-    int lo = 0, hi = a.n_chains - 1;   // the largest c with polylines[c].start <= k: never outside 0 .. n_chains - 1, whatever the table holds
-    while (lo < hi) {
-        const int mid = lo + (hi - lo + 1) / 2;   // lo < mid <= hi
-        if ((long long)a.polylines[4 * (size_t)mid] <= k) lo = mid;
-        else hi = mid - 1;
-    }
+    const int lo = entry_of(a.polylines, a.n_chains, k);   // the polyline the vertex belongs to, if the table is what it should be
     SgSpan t{i0, 0, lo, 0, 0, 0};
-    const int32_t* ch = a.chains + 4 * (size_t)lo;
+    const ChainEntry ch = chain_entry(a.chains, lo, a.n_points);
     const int32_t* pl = a.polylines + 4 * (size_t)lo;
-    const int S = ch[0], L = ch[1], F = ch[2], vs = pl[0], vl = pl[1];
+    const int S = ch.start, L = ch.len, F = ch.flags, vs = pl[0], vl = pl[1];
     const long long p_end = (long long)S + L, v_end = (long long)vs + vl;
-    if (S < 0 || L < 1 || p_end > (long long)a.n_points) return t;   // the chain does not lie inside points
+    if (!CVS_INSIDE_POINTS(S, L, a.n_points)) return t;   // the chain does not lie inside points (ch.ok(), spelled on the locals: the
+                                                          // form that keeps both kernels at their registers)
     if (vs < 0 || k < vs || k >= v_end) return t;                    // the vertex is not one of the polyline the search found
     if (i0 < S || i0 >= p_end) return t;
     t.start = S;
@@ -86,11 +76,11 @@ __device__ __forceinline__ SgPoint sg_point(const SegmentArgs& a, const SgSpan& 
     if (p >= (long long)t.start + t.len) p -= t.len;
     SgPoint q;
     if (a.xy) {
-        const SgFloat2 v = reinterpret_cast<const SgFloat2*>(a.xy)[p];
+        const FloatPair v = reinterpret_cast<const FloatPair*>(a.xy)[p];
         q.dx = (double)v.x - x0;
         q.dy = (double)v.y - y0;
     } else {
-        const SgInt2 v = reinterpret_cast<const SgInt2*>(a.points)[p];
+        const IntPair v = reinterpret_cast<const IntPair*>(a.points)[p];
         q.dx = (double)v.x - x0;
         q.dy = (double)v.y - y0;
     }
@@ -249,7 +239,7 @@ __device__ __forceinline__ void sg_store(uint32_t* table, long long k, const SgS
 
 __device__ __forceinline__ void sg_origin(const SegmentArgs& a, const SgSpan& t, double& x0, double& y0)
 {
-    const SgInt2 o = reinterpret_cast<const SgInt2*>(a.points)[t.first];
+    const IntPair o = reinterpret_cast<const IntPair*>(a.points)[t.first];
     x0 = (double)o.x;
     y0 = (double)o.y;
 }

@@ -11,12 +11,13 @@
 // k_turn_nms: one lane per point; only a point that is eligible and turns sharply enough (cos <= max_cos) walks its window.
 // k_turn_summary: one wave per chain of at most kPlWaveMax points, one 256-lane workgroup per longer chain (ms_long_entries, shared with
 // the measures and the segments), integers and (cos, position) pairs combined by butterfly.
-// What the table says is checked before it is used as an address (tn_entry); coordinates are never addresses.  No atomic, no scratch,
+// What the table says is checked before it is used as an address (chain_entry); coordinates are never addresses.  No atomic, no scratch,
 // nothing read back.
 // Built with -ffp-contract=off: every product, sum and difference below rounds on its own, as the contract in include/cvsteer_hip.h says;
 // the double divisions and square roots are the correctly rounded ones.
 #include <hip/hip_runtime.h>
 
+#include "cvs_chain_device.h"
 #include "cvs_turns.h"
 
 namespace cvs {
@@ -28,34 +29,9 @@ constexpr int kTnTile = kTnBlock + 2 * kTurnMaxRadius;     // staged points: the
 constexpr int kTnNone = 0x7fffffff;                        // "no eligible point yet" in a (cos, position) pair
 static_assert((1ll << 30) / kTnBlock <= (long long)kGridMaxX, "k_turns and k_turn_nms: one workgroup per 256 points never meets the grid bound");
 
-struct TnPair {   // a point as it lies in memory (4-byte aligned): an (x, y) int32 pair of `points`, or the bits of an (xs, ys) pair of `xy`
+struct alignas(8) TnStaged {   // a point (a WordPair: the bits of an (x, y) pair of `points` or of an (xs, ys) pair of `xy`) in LDS
     uint32_t x, y;
 };
-struct alignas(8) TnStaged {   // the same in LDS
-    uint32_t x, y;
-};
-
-// the entry of chain c, and whether it lies inside `points`
-__device__ __forceinline__ bool tn_entry(const TurnArgs& a, int c, int& S, int& L, int& F)
-{
-    const int32_t* e = a.chains + 4 * (size_t)c;
-    S = e[0];
-    L = e[1];
-    F = e[2];
-    return S >= 0 && L >= 1 && (long long)S + L <= (long long)a.n_points;
-}
-
-// the largest c with chains[c].start <= i where the starts ascend; never outside 0 .. n_chains - 1, whatever the table holds
-__device__ __forceinline__ int tn_search(const TurnArgs& a, long long i)
-{
-    int lo = 0, hi = a.n_chains - 1;
-    while (lo < hi) {
-        const int mid = lo + (hi - lo + 1) / 2;   // lo < mid <= hi
-        if ((long long)a.chains[4 * (size_t)mid] <= i) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
 
 __device__ __forceinline__ void tn_store(const TurnArgs& a, long long i, int chain, int flags, int nb, int nf, float sn, float cs, float lb, float lf)
 {
@@ -132,13 +108,13 @@ __global__ __launch_bounds__(kTnBlock) void k_turns(const TurnArgs a)
     __shared__ TnStaged tile[kTnTile];
     const int tid = threadIdx.x;
     const long long n = a.n_points, base = (long long)blockIdx.x * kTnBlock;
-    const TnPair* src = reinterpret_cast<const TnPair*>(a.xy ? static_cast<const void*>(a.xy) : static_cast<const void*>(a.points));
+    const WordPair* src = reinterpret_cast<const WordPair*>(a.xy ? static_cast<const void*>(a.xy) : static_cast<const void*>(a.points));
     const bool sub = a.xy != nullptr;
     // the window [lo, hi) of `points` this workgroup stages: hi - lo <= kTnBlock + 2 radius <= kTnTile
     const long long lo = base - a.radius < 0 ? 0 : base - a.radius;
     const long long hi = base + kTnBlock + a.radius > n ? n : base + kTnBlock + a.radius;
     for (long long p = lo + tid; p < hi; p += kTnBlock) {
-        const TnPair v = src[p];
+        const WordPair v = src[p];
         tile[p - lo].x = v.x;
         tile[p - lo].y = v.y;
     }
@@ -147,14 +123,15 @@ __global__ __launch_bounds__(kTnBlock) void k_turns(const TurnArgs a)
     if (i >= n) return;
 
     const float qnan = __uint_as_float(0x7fc00000u);
-    const int c = tn_search(a, i);
-    int S, L, F;
-    if (!tn_entry(a, c, S, L, F) || i < S || i >= (long long)S + L) {
+    const int c = entry_of(a.chains, a.n_chains, i);
+    const ChainEntry e = chain_entry(a.chains, c, a.n_points);
+    const int S = e.start, L = e.len, F = e.flags;
+    if (!e.ok() || i < S || i >= (long long)S + L) {   // a point of a broken entry, or of none
         tn_store(a, i, -1, kTurnNoChain, 0, 0, qnan, qnan, 0.0f, 0.0f);
         return;
     }
     auto coords = [&](long long p, double& x, double& y) {   // S <= p < S + L <= n_points
-        TnPair v;
+        WordPair v;
         if (p >= lo && p < hi) {
             const TnStaged t = tile[p - lo];
             v.x = t.x;
@@ -237,10 +214,12 @@ __global__ __launch_bounds__(kTnBlock) void k_turn_nms(const TurnArgs a)
     if (flags & kTurnIneligible) return;
     const float ci = __uint_as_float(r[5]);
     if (!(ci <= a.max_cos)) return;
-    int S, L, F;
-    if (c < 0 || c >= a.n_chains || !tn_entry(a, c, S, L, F) || i < S || i >= (long long)S + L) return;   // (launch 1 has checked all this)
+    if (c < 0 || c >= a.n_chains) return;   // (launch 1 has checked this, and what follows)
+    const ChainEntry e = chain_entry(a.chains, c, a.n_points);
+    const int S = e.start, L = e.len;
+    if (!e.ok() || i < S || i >= (long long)S + L) return;
     const int j = (int)(i - S);
-    const bool closed = (F & kChainClosed) != 0;
+    const bool closed = (e.flags & kChainClosed) != 0;
     const int reach = closed ? min(a.nms, (L - 1) / 2) : a.nms;
     for (int k = 1; k <= reach; ++k) {
         int jb = j - k, jf = j + k;
@@ -273,26 +252,25 @@ __global__ __launch_bounds__(256) void k_turn_summary(const TurnArgs a)
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     // one wave per chain of at most kPlWaveMax points, and the summary of every entry that does not lie inside `points`
     for (long long c = (long long)blockIdx.x * 4 + wave; c < a.n_chains; c += (long long)gridDim.x * 4) {
-        int S, L, F;
-        const bool ok = tn_entry(a, (int)c, S, L, F);
-        if (ok && L > kPlWaveMax) continue;   // a workgroup's, below
+        const ChainEntry e = chain_entry(a.chains, (int)c, a.n_points);
+        const bool ok = e.ok();
+        if (ok && e.len > kPlWaveMax) continue;   // a workgroup's, below
         TnSum s{0, 0, kTnNone, 0.0f};
         if (ok)
-            for (int j = lane; j < L; j += 64) tn_take(s, a, (long long)S + j, (int)c);
+            for (int j = lane; j < e.len; j += 64) tn_take(s, a, (long long)e.start + j, (int)c);
         tn_wave(s);
         if (lane == 0) tn_store_summary(a, c, s);
     }
     ms_long_entries(
         a.n_chains, lm,
         [&](long long c) {
-            int S, L, F;
-            return tn_entry(a, (int)c, S, L, F) && L > kPlWaveMax;
+            const ChainEntry e = chain_entry(a.chains, (int)c, a.n_points);
+            return e.ok() && e.len > kPlWaveMax;
         },
         [&](long long c) {
-            int S, L, F;
-            tn_entry(a, (int)c, S, L, F);
+            const ChainEntry e = chain_entry(a.chains, (int)c, a.n_points);
             TnSum s{0, 0, kTnNone, 0.0f};
-            for (int j = tid; j < L; j += 256) tn_take(s, a, (long long)S + j, (int)c);
+            for (int j = tid; j < e.len; j += 256) tn_take(s, a, (long long)e.start + j, (int)c);
             tn_wave(s);
             __syncthreads();   // `part` is free again: the chain before has been read to its end
             if (lane == 0) part[wave] = s;

@@ -13,12 +13,6 @@ using namespace cvs;
 
 static_assert(sizeof(cvs_chain) == 16, "cvs_chain: four 4-byte fields (k_pl_apply writes it as four words)");
 
-namespace {
-
-bool misaligned(const void* p) { return reinterpret_cast<uintptr_t>(p) % alignof(int32_t) != 0; }
-
-}  // namespace
-
 int cvs_chain_polylines(cvs_handle h, const int32_t* points, int n_points, const cvs_chain* chains, int n_chains, float eps, int32_t* vertices,
                         int vertex_capacity, int32_t* index, cvs_chain* polylines, int mem, int* n_vertices)
 {
@@ -35,9 +29,7 @@ int cvs_chain_polylines(cvs_handle h, const int32_t* points, int n_points, const
     if (n_points > (1 << 30)) return fail(h, CVS_E_SIZE, "more than 2^30 points");
     const bool host = mem == CVS_MEM_HOST;
     if (host)
-        for (int c = 0; c < n_chains; ++c)
-            if (chains[c].start < 0 || chains[c].length < 1 || (long long)chains[c].start + chains[c].length > n_points)
-                return fail(h, CVS_E_BADARG, "a chain does not lie inside points");
+        if (const char* what = chain_table_outside(n_points, reinterpret_cast<const int32_t*>(chains), n_chains)) return fail(h, CVS_E_BADARG, what);
     int rc;
     if ((rc = refuse_capture(h, "cvs_chain_polylines reads its count back: not capturable"))) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
@@ -50,24 +42,19 @@ int cvs_chain_polylines(cvs_handle h, const int32_t* points, int n_points, const
     // n_vertices <= n_points: the staged outputs never need more than that
     const int cap_v = std::min(vertex_capacity, n_points), blocks = pl_scan_blocks(n_chains);
     hipStream_t s = h->stream;
-    Scratch sc;
-    const size_t o_keep = sc.reserve((size_t)n_points), o_cnt = sc.reserve((size_t)n_chains * 4), o_part = sc.reserve(((size_t)blocks + 1) * 4);
-    const size_t o_pts = host ? sc.reserve((size_t)n_points * 8) : 0, o_chn = host ? sc.reserve((size_t)n_chains * sizeof(cvs_chain)) : 0;
-    const size_t o_vtx = host ? sc.reserve((size_t)cap_v * 8) : 0, o_idx = host && index ? sc.reserve((size_t)cap_v * 4) : 0;
-    const size_t o_pol = host ? sc.reserve((size_t)n_chains * sizeof(cvs_chain)) : 0;
-    if ((rc = grow_scratch(h, "hipMalloc(&h->ch_scr, need)", h->ch_scr, h->ch_scr_bytes, sc.need, 1))) return rc;
-    uint8_t* keep = h->ch_scr + o_keep;
-    int32_t* cnt = reinterpret_cast<int32_t*>(h->ch_scr + o_cnt);
-    int32_t* part = reinterpret_cast<int32_t*>(h->ch_scr + o_part);
-    const int32_t* dpts = host ? reinterpret_cast<int32_t*>(h->ch_scr + o_pts) : points;
-    const int32_t* dchn = host ? reinterpret_cast<int32_t*>(h->ch_scr + o_chn) : reinterpret_cast<const int32_t*>(chains);
-    int32_t* dvtx = host ? reinterpret_cast<int32_t*>(h->ch_scr + o_vtx) : vertices;
-    int32_t* didx = host ? (index ? reinterpret_cast<int32_t*>(h->ch_scr + o_idx) : nullptr) : index;
-    int32_t* dpol = host ? reinterpret_cast<int32_t*>(h->ch_scr + o_pol) : reinterpret_cast<int32_t*>(polylines);
-    if (host) {
-        if (n_points) HIP_TRY(h, hipMemcpyAsync(h->ch_scr + o_pts, points, (size_t)n_points * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(h, hipMemcpyAsync(h->ch_scr + o_chn, chains, (size_t)n_chains * sizeof(cvs_chain), hipMemcpyHostToDevice, s));
-    }
+    uint8_t* keep;
+    int32_t *cnt, *part, *dvtx, *didx, *dpol;
+    const int32_t *dpts, *dchn;
+    Staged st(h, "cvs_chain_polylines", host);
+    st.scratch(keep, (size_t)n_points);
+    st.scratch(cnt, (size_t)n_chains * 4);
+    st.scratch(part, ((size_t)blocks + 1) * 4);
+    st.in(dpts, points, (size_t)n_points * 8);
+    st.in(dchn, chains, (size_t)n_chains * sizeof(cvs_chain));
+    st.out(dvtx, vertices, (size_t)cap_v * 8);   // (fetched below, once the count is known: `total` records, not cap_v)
+    st.out(didx, index, (size_t)cap_v * 4);
+    st.out(dpol, polylines, (size_t)n_chains * sizeof(cvs_chain));
+    if ((rc = st.commit()) || (rc = st.upload(s))) return rc;
 
     // the launch sequence: a function of (n_points, n_chains) alone; the kernels themselves hold back every store when the total does not fit
     const double e2 = (double)eps * (double)eps;

@@ -15,24 +15,6 @@ static_assert(sizeof(cvs_chain_measure) == kMeasureWords * 4 && offsetof(cvs_cha
                   offsetof(cvs_chain_measure, sum) == 24 && offsetof(cvs_chain_measure, length) == 32,
               "cvs_chain_measure: the ten words ms_store writes");
 
-namespace {
-
-bool misaligned(const void* p) { return reinterpret_cast<uintptr_t>(p) % alignof(int32_t) != 0; }
-
-// an array of `n` records of `words` 4-byte words as a plane, for the overlap rule of the contour tail (check_disjoint)
-cvs_plane array_plane(const void* p, int n, int words, int mem)
-{
-    cvs_plane q{};
-    q.data = n > 0 ? const_cast<float*>(static_cast<const float*>(p)) : nullptr;
-    q.rows = n;
-    q.cols = words;
-    q.step = (size_t)words * 4;
-    q.mem = mem;
-    return q;
-}
-
-}  // namespace
-
 int cvs_chain_refine(cvs_handle h, const cvs_plane* map, const cvs_plane* theta, const int32_t* points, int n_points, float* xy, float* strength,
                      int mem)
 {
@@ -68,18 +50,11 @@ int cvs_chain_refine(cvs_handle h, const cvs_plane* map, const cvs_plane* theta,
     a.rows = h->rows;
     a.cols = h->cols;
     a.n_points = n_points;
-    a.points = points;
-    a.xy = xy;
-    a.strength = strength;
-    if (host) {
-        Scratch sc;
-        const size_t o_pts = sc.reserve((size_t)n_points * 8), o_xy = sc.reserve((size_t)n_points * 8), o_str = sc.reserve((size_t)n_points * 4);
-        if ((rc = grow_scratch(h, "hipMalloc(&h->ch_scr, need)", h->ch_scr, h->ch_scr_bytes, sc.need, 1))) return rc;
-        HIP_TRY(h, hipMemcpyAsync(h->ch_scr + o_pts, points, (size_t)n_points * 8, hipMemcpyHostToDevice, s));
-        a.points = reinterpret_cast<const int32_t*>(h->ch_scr + o_pts);
-        a.xy = reinterpret_cast<float*>(h->ch_scr + o_xy);
-        a.strength = strength ? reinterpret_cast<float*>(h->ch_scr + o_str) : nullptr;
-    }
+    Staged st(h, "cvs_chain_refine", host);
+    st.in(a.points, points, (size_t)n_points * 8);
+    st.out(a.xy, xy, (size_t)n_points * 8);
+    st.out(a.strength, strength, (size_t)n_points * 4);
+    if ((rc = st.commit()) || (rc = st.upload(s))) return rc;
     if ((rc = in_ref(c, map, a.map))) return rc;
     if (theta) {
         if ((rc = in_ref(c, theta, a.theta))) return rc;
@@ -87,11 +62,8 @@ int cvs_chain_refine(cvs_handle h, const cvs_plane* map, const cvs_plane* theta,
         a.theta = own;
     }
     HIP_TRY(h, launch_chain_refine(a, s));
-    if (host) {
-        HIP_TRY(h, hipMemcpyAsync(xy, a.xy, (size_t)n_points * 8, hipMemcpyDeviceToHost, s));
-        if (strength) HIP_TRY(h, hipMemcpyAsync(strength, a.strength, (size_t)n_points * 4, hipMemcpyDeviceToHost, s));
-    }
-    if (sync) HIP_TRY(h, hipStreamSynchronize(s));
+    if ((rc = st.download(s))) return rc;
+    if (sync) HIP_TRY(h, hipStreamSynchronize(s));   // (a DEVICE call with a host plane waits too)
     return CVS_OK;
 }
 
@@ -112,9 +84,7 @@ int cvs_chain_measures(cvs_handle h, const int32_t* points, int n_points, const 
     if ((rc = check_disjoint(h, ins, 4, &out, 1))) return rc;
     const bool host = mem == CVS_MEM_HOST;
     if (host)
-        for (int c = 0; c < n_chains; ++c)
-            if (chains[c].start < 0 || chains[c].length < 1 || (long long)chains[c].start + chains[c].length > n_points)
-                return fail(h, CVS_E_BADARG, "a chain does not lie inside points");
+        if (const char* what = chain_table_outside(n_points, reinterpret_cast<const int32_t*>(chains), n_chains)) return fail(h, CVS_E_BADARG, what);
     if (host && (rc = refuse_capture(h, "cvs_chain_measures stages host memory and synchronises: not capturable"))) return rc;
     if (n_chains == 0) return CVS_OK;
     HIP_TRY(h, hipSetDevice(h->device));
@@ -122,35 +92,17 @@ int cvs_chain_measures(cvs_handle h, const int32_t* points, int n_points, const 
 
     hipStream_t s = h->stream;
     MeasureArgs a{};
-    a.points = points;
     a.n_points = n_points;
-    a.chains = reinterpret_cast<const int32_t*>(chains);
     a.n_chains = n_chains;
-    a.xy = xy;
-    a.strength = strength;
-    a.table = reinterpret_cast<uint32_t*>(table);
-    if (host) {
-        Scratch sc;
-        const size_t o_pts = sc.reserve((size_t)n_points * 8), o_chn = sc.reserve((size_t)n_chains * sizeof(cvs_chain));
-        const size_t o_xy = sc.reserve(xy ? (size_t)n_points * 8 : 0), o_str = sc.reserve(strength ? (size_t)n_points * 4 : 0);
-        const size_t o_tab = sc.reserve((size_t)n_chains * sizeof(cvs_chain_measure));
-        if ((rc = grow_scratch(h, "hipMalloc(&h->ch_scr, need)", h->ch_scr, h->ch_scr_bytes, sc.need, 1))) return rc;
-        if (n_points) HIP_TRY(h, hipMemcpyAsync(h->ch_scr + o_pts, points, (size_t)n_points * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(h, hipMemcpyAsync(h->ch_scr + o_chn, chains, (size_t)n_chains * sizeof(cvs_chain), hipMemcpyHostToDevice, s));
-        if (xy && n_points) HIP_TRY(h, hipMemcpyAsync(h->ch_scr + o_xy, xy, (size_t)n_points * 8, hipMemcpyHostToDevice, s));
-        if (strength && n_points) HIP_TRY(h, hipMemcpyAsync(h->ch_scr + o_str, strength, (size_t)n_points * 4, hipMemcpyHostToDevice, s));
-        a.points = reinterpret_cast<const int32_t*>(h->ch_scr + o_pts);
-        a.chains = reinterpret_cast<const int32_t*>(h->ch_scr + o_chn);
-        a.xy = xy ? reinterpret_cast<const float*>(h->ch_scr + o_xy) : nullptr;
-        a.strength = strength ? reinterpret_cast<const float*>(h->ch_scr + o_str) : nullptr;
-        a.table = reinterpret_cast<uint32_t*>(h->ch_scr + o_tab);
-    }
+    Staged st(h, "cvs_chain_measures", host);
+    st.in(a.points, points, (size_t)n_points * 8);
+    st.in(a.chains, chains, (size_t)n_chains * sizeof(cvs_chain));
+    st.in(a.xy, xy, (size_t)n_points * 8);
+    st.in(a.strength, strength, (size_t)n_points * 4);
+    st.out(a.table, table, (size_t)n_chains * sizeof(cvs_chain_measure));
+    if ((rc = st.commit()) || (rc = st.upload(s))) return rc;
     // two launches for any table: the launch sequence is a function of (n_points, n_chains) alone
     HIP_TRY(h, launch_measure_wave(a, s));
     HIP_TRY(h, launch_measure_block(a, s));
-    if (host) {
-        HIP_TRY(h, hipMemcpyAsync(table, a.table, (size_t)n_chains * sizeof(cvs_chain_measure), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipStreamSynchronize(s));
-    }
-    return CVS_OK;
+    return st.fetch(s);
 }

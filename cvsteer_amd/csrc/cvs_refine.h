@@ -35,30 +35,4 @@ struct MeasureArgs {
 hipError_t launch_measure_wave(const MeasureArgs& a, hipStream_t s);
 hipError_t launch_measure_block(const MeasureArgs& a, hipStream_t s);
 
-#ifdef __HIPCC__
-// the long entries of a table of n entries, for the _block kernels (those of the measures and of cvs_kernels_segments.hip): a 256-lane
-// workgroup takes slices of 256 entries (slice = blockIdx.x, + gridDim.x, ...), ballots is_long(entry) and calls f(entry) for each entry
-// that is, all 256 lanes together.  lm: four words of LDS.
-template <class P, class F>
-__device__ __forceinline__ void ms_long_entries(long long n, unsigned long long* lm, P is_long, F f)
-{
-    for (long long base = (long long)blockIdx.x * 256; base < n; base += (long long)gridDim.x * 256) {
-        const long long c = base + threadIdx.x;
-        const unsigned long long b = __ballot(c < n && is_long(c));
-        if ((threadIdx.x & 63) == 0) lm[threadIdx.x >> 6] = b;
-        __syncthreads();
-#pragma unroll 1
-        for (int w = 0; w < 4; ++w) {
-            unsigned long long bits = lm[w];
-            while (bits) {
-                const int k = __ffsll((long long)bits) - 1;
-                bits &= bits - 1;
-                f(base + w * 64 + k);
-            }
-        }
-        __syncthreads();   // lm is written again
-    }
-}
-#endif
-
 }  // namespace cvs

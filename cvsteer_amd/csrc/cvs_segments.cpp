@@ -18,28 +18,14 @@ static_assert(CVS_SEG_WRAPS == kSegWraps && CVS_SEG_DEGENERATE == kSegDegenerate
 
 namespace {
 
-bool misaligned(const void* p, size_t to = alignof(int32_t)) { return reinterpret_cast<uintptr_t>(p) % to != 0; }
-
-// an array of `n` records of `words` 4-byte words as a plane, for the overlap rule of the contour tail (check_disjoint)
-cvs_plane array_plane(const void* p, int n, int words, int mem)
-{
-    cvs_plane q{};
-    q.data = n > 0 ? const_cast<float*>(static_cast<const float*>(p)) : nullptr;
-    q.rows = n;
-    q.cols = words;
-    q.step = (size_t)words * 4;
-    q.mem = mem;
-    return q;
-}
-
-// what a HOST call is refused for: nullptr if the three tables say what the contract says
+// what a HOST call is refused for: nullptr if the three tables say what the contract says (entry by entry: the chain, then its polyline)
 const char* host_tables_wrong(int n_points, const cvs_chain* chains, const cvs_chain* polylines, int n_chains, const int32_t* index,
                               int n_vertices)
 {
     long long at = 0;
     for (int c = 0; c < n_chains; ++c) {
         const cvs_chain &t = chains[c], &p = polylines[c];
-        if (t.start < 0 || t.length < 1 || (long long)t.start + t.length > n_points) return "a chain does not lie inside points";
+        if (const char* what = chain_entry_outside(n_points, reinterpret_cast<const int32_t*>(chains), (size_t)c)) return what;
         if (p.start != at || p.length < 0 || at + p.length > n_vertices) return "the polyline starts are not the running sum of the lengths";
         for (long long k = at; k < at + p.length; ++k) {
             if (index[k] < t.start || index[k] >= t.start + t.length) return "an index leaves its chain";
@@ -81,44 +67,20 @@ int cvs_polyline_segments(cvs_handle h, const int32_t* points, int n_points, con
 
     hipStream_t s = h->stream;
     SegmentArgs a{};
-    a.points = points;
     a.n_points = n_points;
-    a.chains = reinterpret_cast<const int32_t*>(chains);
-    a.polylines = reinterpret_cast<const int32_t*>(polylines);
     a.n_chains = n_chains;
-    a.index = index;
     a.n_vertices = n_vertices;
-    a.xy = xy;
-    a.strength = strength;
-    a.table = reinterpret_cast<uint32_t*>(table);
-    if (host) {
-        const size_t b_pts = (size_t)n_points * 8, b_tab = (size_t)n_chains * sizeof(cvs_chain), b_idx = (size_t)n_vertices * 4;
-        const size_t b_xy = xy ? b_pts : 0, b_str = strength ? (size_t)n_points * 4 : 0, b_out = (size_t)n_vertices * sizeof(cvs_segment);
-        Scratch sc;
-        const size_t o_out = sc.reserve(b_out), o_pts = sc.reserve(b_pts), o_chn = sc.reserve(b_tab), o_pol = sc.reserve(b_tab);
-        const size_t o_idx = sc.reserve(b_idx), o_xy = sc.reserve(b_xy), o_str = sc.reserve(b_str);
-        if ((rc = grow_scratch(h, "hipMalloc(&h->ch_scr, need)", h->ch_scr, h->ch_scr_bytes, sc.need, 1))) return rc;
-        const struct {
-            const void* src;
-            size_t off, bytes;
-        } up[6] = {{points, o_pts, b_pts}, {chains, o_chn, b_tab}, {polylines, o_pol, b_tab}, {index, o_idx, b_idx}, {xy, o_xy, b_xy},
-                   {strength, o_str, b_str}};
-        for (const auto& u : up)
-            if (u.bytes) HIP_TRY(h, hipMemcpyAsync(h->ch_scr + u.off, u.src, u.bytes, hipMemcpyHostToDevice, s));
-        a.points = reinterpret_cast<const int32_t*>(h->ch_scr + o_pts);
-        a.chains = reinterpret_cast<const int32_t*>(h->ch_scr + o_chn);
-        a.polylines = reinterpret_cast<const int32_t*>(h->ch_scr + o_pol);
-        a.index = reinterpret_cast<const int32_t*>(h->ch_scr + o_idx);
-        a.xy = xy ? reinterpret_cast<const float*>(h->ch_scr + o_xy) : nullptr;
-        a.strength = strength ? reinterpret_cast<const float*>(h->ch_scr + o_str) : nullptr;
-        a.table = reinterpret_cast<uint32_t*>(h->ch_scr + o_out);
-    }
+    Staged st(h, "cvs_polyline_segments", host);
+    st.in(a.points, points, (size_t)n_points * 8);
+    st.in(a.chains, chains, (size_t)n_chains * sizeof(cvs_chain));
+    st.in(a.polylines, polylines, (size_t)n_chains * sizeof(cvs_chain));
+    st.in(a.index, index, (size_t)n_vertices * 4);
+    st.in(a.xy, xy, (size_t)n_points * 8);
+    st.in(a.strength, strength, (size_t)n_points * 4);
+    st.out(a.table, table, (size_t)n_vertices * sizeof(cvs_segment));
+    if ((rc = st.commit()) || (rc = st.upload(s))) return rc;
     // two launches for any table: the launch sequence is a function of n_vertices alone
     HIP_TRY(h, launch_segments_wave(a, s));
     HIP_TRY(h, launch_segments_block(a, s));
-    if (host) {
-        HIP_TRY(h, hipMemcpyAsync(table, a.table, (size_t)n_vertices * sizeof(cvs_segment), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipStreamSynchronize(s));
-    }
-    return CVS_OK;
+    return st.fetch(s);
 }

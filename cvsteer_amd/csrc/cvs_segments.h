@@ -1,6 +1,6 @@
 // cvs_segments.h -- launch descriptor of the contour-segment kernels (cvs_kernels_segments.hip), shared with their C-ABI layer
 // (cvs_segments.cpp).  The chain table and kChainClosed are those of cvs_chains.h, the polyline table and the index those of cvs_polyline.h,
-// the wave / workgroup split (kPlWaveMax, kPlMaxGrid) and the search for long entries (ms_long_entries) those of cvs_refine.h.
+// the wave / workgroup split (kPlWaveMax, kPlMaxGrid) that of cvs_polyline.h.
 #pragma once
 #include "cvs_refine.h"
 

@@ -1,5 +1,5 @@
 // cvs_turns.cpp -- the C ABI of the contour turns (extension): cvs_chain_turns.  Argument checks, the check of a host chain table
-// (turns_host_table_wrong, cvs_turns.h), staging of host arrays in the handle's scratch (cvs_context::ch_scr) and the two or three launches
+// (chain_table_not_running_sum, cvs_chain_table.h), staging of host arrays in the handle's scratch (cvs_context::ch_scr) and the two or three launches
 // of cvs_kernels_turns.hip.  Nothing is read back; no arithmetic on coordinates happens here.
 #include <hip/hip_runtime_api.h>
 
@@ -20,24 +20,6 @@ static_assert(CVS_TURN_CORNER == kTurnCorner && CVS_TURN_END == kTurnEnd && CVS_
                   CVS_TURN_SHORT == kTurnShort && CVS_TURN_NO_CHAIN == kTurnNoChain,
               "the flags the turn kernels write");
 static_assert(sizeof(cvs_turn_cfg) == 16 && sizeof(cvs_chain) == 16, "the structs of the turn call");
-
-namespace {
-
-bool misaligned(const void* p) { return reinterpret_cast<uintptr_t>(p) % alignof(int32_t) != 0; }
-
-// an array of `n` records of `words` 4-byte words as a plane, for the overlap rule of the contour tail (check_disjoint)
-cvs_plane array_plane(const void* p, int n, int words, int mem)
-{
-    cvs_plane q{};
-    q.data = n > 0 ? const_cast<float*>(static_cast<const float*>(p)) : nullptr;
-    q.rows = n;
-    q.cols = words;
-    q.step = (size_t)words * 4;
-    q.mem = mem;
-    return q;
-}
-
-}  // namespace
 
 int cvs_chain_turns(cvs_handle h, const int32_t* points, int n_points, const cvs_chain* chains, int n_chains, const float* xy,
                     const cvs_turn_cfg* cfg, cvs_chain_turn* table, cvs_turn_summary* summary, int mem)
@@ -62,7 +44,7 @@ int cvs_chain_turns(cvs_handle h, const int32_t* points, int n_points, const cvs
     if ((rc = check_disjoint(h, ins, 3, outs, 2))) return rc;
     const bool host = mem == CVS_MEM_HOST;
     if (host)
-        if (const char* what = turns_host_table_wrong(n_points, reinterpret_cast<const int32_t*>(chains), n_chains)) return fail(h, CVS_E_BADARG, what);
+        if (const char* what = chain_table_not_running_sum(n_points, reinterpret_cast<const int32_t*>(chains), n_chains)) return fail(h, CVS_E_BADARG, what);
     if (host && (rc = refuse_capture(h, "cvs_chain_turns stages host memory and synchronises: not capturable"))) return rc;
     if (n_points == 0) return CVS_OK;
     HIP_TRY(h, hipSetDevice(h->device));
@@ -70,44 +52,22 @@ int cvs_chain_turns(cvs_handle h, const int32_t* points, int n_points, const cvs
 
     hipStream_t s = h->stream;
     TurnArgs a{};
-    a.points = points;
     a.n_points = n_points;
-    a.chains = reinterpret_cast<const int32_t*>(chains);
     a.n_chains = n_chains;
-    a.xy = xy;
     a.radius = cfg->radius;
     a.min_arm = cfg->min_arm;
     a.nms = cfg->nms;
     a.max_cos = cfg->max_cos;
-    a.table = reinterpret_cast<uint32_t*>(table);
-    a.summary = reinterpret_cast<uint32_t*>(summary);
-    const size_t b_out = (size_t)n_points * sizeof(cvs_chain_turn), b_sum = summary ? (size_t)n_chains * sizeof(cvs_turn_summary) : 0;
-    if (host) {
-        const size_t b_pts = (size_t)n_points * 8, b_tab = (size_t)n_chains * sizeof(cvs_chain), b_xy = xy ? b_pts : 0;
-        Scratch sc;
-        const size_t o_out = sc.reserve(b_out), o_sum = sc.reserve(b_sum), o_pts = sc.reserve(b_pts), o_chn = sc.reserve(b_tab);
-        const size_t o_xy = sc.reserve(b_xy);
-        if ((rc = grow_scratch(h, "hipMalloc(&h->ch_scr, need)", h->ch_scr, h->ch_scr_bytes, sc.need, 1))) return rc;
-        const struct {
-            const void* src;
-            size_t off, bytes;
-        } up[3] = {{points, o_pts, b_pts}, {chains, o_chn, b_tab}, {xy, o_xy, b_xy}};
-        for (const auto& u : up)
-            if (u.bytes) HIP_TRY(h, hipMemcpyAsync(h->ch_scr + u.off, u.src, u.bytes, hipMemcpyHostToDevice, s));
-        a.points = reinterpret_cast<const int32_t*>(h->ch_scr + o_pts);
-        a.chains = reinterpret_cast<const int32_t*>(h->ch_scr + o_chn);
-        a.xy = xy ? reinterpret_cast<const float*>(h->ch_scr + o_xy) : nullptr;
-        a.table = reinterpret_cast<uint32_t*>(h->ch_scr + o_out);
-        a.summary = summary ? reinterpret_cast<uint32_t*>(h->ch_scr + o_sum) : nullptr;
-    }
+    Staged st(h, "cvs_chain_turns", host);
+    st.in(a.points, points, (size_t)n_points * 8);
+    st.in(a.chains, chains, (size_t)n_chains * sizeof(cvs_chain));
+    st.in(a.xy, xy, (size_t)n_points * 8);
+    st.out(a.table, table, (size_t)n_points * sizeof(cvs_chain_turn));
+    st.out(a.summary, summary, (size_t)n_chains * sizeof(cvs_turn_summary));
+    if ((rc = st.commit()) || (rc = st.upload(s))) return rc;
     // two launches for any table, three with a summary: the launch sequence is a function of (n_points, n_chains, summary != NULL) alone
     HIP_TRY(h, launch_turns(a, s));
     HIP_TRY(h, launch_turn_nms(a, s));
     if (a.summary) HIP_TRY(h, launch_turn_summary(a, s));
-    if (host) {
-        HIP_TRY(h, hipMemcpyAsync(table, a.table, b_out, hipMemcpyDeviceToHost, s));
-        if (summary) HIP_TRY(h, hipMemcpyAsync(summary, a.summary, b_sum, hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipStreamSynchronize(s));
-    }
-    return CVS_OK;
+    return st.fetch(s);
 }

@@ -231,6 +231,28 @@ def test_capacity_errors_and_run_to_run_identity():
     assert len(f.chain_polylines(dp, dt, 1.0)) == 2
 
 
+def test_an_array_that_is_not_aligned_to_4_bytes_is_refused():
+    """each of the five arrays in turn two bytes off, on both paths: CVS_E_BADARG, the count and every output untouched (one entry fewer
+    is passed than the arrays hold, so that nothing could be read behind them)"""
+    f = _filters()
+    pts, table = _random_chains(0.3)
+    npts, nch = len(pts), len(table)
+    dev = [torch.from_numpy(np.array(pts)).to(DEV), torch.from_numpy(np.array(table)).to(DEV),
+           torch.full((npts, 2), -9, dtype=torch.int32, device=DEV), torch.full((npts,), -9, dtype=torch.int32, device=DEV),
+           torch.full((nch, 4), -9, dtype=torch.int32, device=DEV)]
+    host = [np.array(pts), np.array(table), np.full((npts, 2), -9, np.int32), np.full((npts,), -9, np.int32), np.full((nch, 4), -9, np.int32)]
+    f._bind_stream(dev[0])
+    for arrays, mem in ((dev, L.MEM_DEVICE), (host, L.MEM_HOST)):
+        for k in range(5):
+            p = [C.c_void_p((a.data_ptr() if torch.is_tensor(a) else a.ctypes.data) + (2 if j == k else 0)) for j, a in enumerate(arrays)]
+            n = C.c_int(-7)
+            rc = L.lib().cvs_chain_polylines(f._h, p[0], npts - 1, p[1], nch - 1, 1.0, p[2], npts - 1, p[3], p[4], mem, C.byref(n))
+            assert (rc, n.value) == (L.E_BADARG, -7), (mem, k)
+            assert b"not aligned to 4 bytes" in L.lib().cvs_last_error(f._h), (mem, k)
+    torch.cuda.synchronize()
+    assert all(bool((a == -9).all()) for a in dev[2:]) and all((a == -9).all() for a in host[2:])
+
+
 def test_capture_is_refused_and_the_handle_works_afterwards():
     f = cv.SteerableFiltersG2(None)
     pts, table = _random_chains(0.15)

@@ -100,21 +100,25 @@ def test_join_kernels_use_no_scratch(tmp_path):
     assert len(scratch) == 3 and all(v == 0 for v in scratch.values()), scratch
 
 
-def test_host_table_check_under_the_host_sanitizers(tmp_path):
-    """joins_host_table_wrong of cvs_joins.h, compiled without HIP into a stand-alone program with -fsanitize=address,undefined and run
-    over valid and broken tables of exactly their size on the heap: a read past a table would end the program"""
-    exe = os.path.join(str(tmp_path), "joins_host_san")
+def test_chain_table_rules_under_the_host_sanitizers(tmp_path):
+    """The rules of a HOST chain table and the size of the join scratch (cvs_chain_table.h: what cvs_chain_turns and cvs_chain_joins, and
+    cvs_chain_polylines, cvs_chain_measures and cvs_polyline_segments, refuse a table for), compiled without HIP into one stand-alone
+    program with -fsanitize=address,undefined and run over valid and broken tables of exactly their size on the heap: a read past a table
+    would end the program"""
+    exe = os.path.join(str(tmp_path), "chain_table_san")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", "-I" + SRC, "-o", exe, os.path.join(ROOT, "tests", "cpp", "joins_host_san.cpp")])
+                           "-fno-sanitize-recover=all", "-I" + SRC, "-o", exe, os.path.join(ROOT, "tests", "cpp", "chain_table_san.cpp")])
     r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0 and "joins host table OK" in r.stdout, r.stdout + r.stderr
-    # the model's rule is the same rule
+    assert r.returncode == 0 and "chain table OK" in r.stdout, r.stdout + r.stderr
+    # the rule of both models is the same rule
     ok = np.int32([[0, 3, 0, 0], [3, 1, 1, 0], [4, 5, 0, 7]])
-    assert not M.host_table_wrong(9, ok) and M.host_table_wrong(10, ok) and M.host_table_wrong(8, ok) and not M.host_table_wrong(0, ok[:0])
-    for row, col, val in ((1, 0, 2), (1, 1, 0), (2, 1, 6), (0, 0, 1), (0, 1, -1)):
-        bad = ok.copy()
-        bad[row, col] = val
-        assert M.host_table_wrong(9, bad), (row, col, val)
+    for model in (M, TM):
+        assert not model.host_table_wrong(9, ok) and model.host_table_wrong(10, ok) and model.host_table_wrong(8, ok)
+        assert not model.host_table_wrong(0, ok[:0])
+        for row, col, val in ((1, 0, 2), (1, 1, 0), (2, 1, 6), (0, 0, 1), (0, 1, -1)):
+            bad = ok.copy()
+            bad[row, col] = val
+            assert model.host_table_wrong(9, bad), (model.__name__, row, col, val)
 
 
 # ---- the model on its own: hand-made junctions ----

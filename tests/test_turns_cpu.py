@@ -1,5 +1,5 @@
 """Contour turns (cvs_chain_turns) at every layer that exists without a GPU: the public header, the exports of both libraries, the Python
-surface, the generated code of the new kernels (no scratch), the host table check under the host sanitizers as a stand-alone program, and
+surface, the generated code of the new kernels (no scratch; the host table check runs under the host sanitizers in test_joins_cpu.py), and
 the model of turns_model.py that the GPU tests hold the kernels against -- hand cases with known answers, and the geometry of digital
 lines, circles and squares: corners are told from curves."""
 import ctypes as C
@@ -98,23 +98,6 @@ def test_turn_kernels_use_no_scratch(tmp_path):
     for stem in ("k_turns", "k_turn_nms", "k_turn_summary"):
         assert any(stem in n for n in scratch), (stem, sorted(scratch))
     assert len(scratch) == 3 and all(v == 0 for v in scratch.values()), scratch
-
-
-def test_host_table_check_under_the_host_sanitizers(tmp_path):
-    """turns_host_table_wrong of cvs_turns.h, compiled without HIP into a stand-alone program with -fsanitize=address,undefined and run
-    over valid and broken tables of exactly their size on the heap: a read past a table would end the program"""
-    exe = os.path.join(str(tmp_path), "turns_host_san")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", "-I" + SRC, "-o", exe, os.path.join(ROOT, "tests", "cpp", "turns_host_san.cpp")])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0 and "turns host table OK" in r.stdout, r.stdout + r.stderr
-    # the model's rule is the same rule
-    ok = np.int32([[0, 3, 0, 0], [3, 1, 1, 0], [4, 5, 0, 7]])
-    assert not M.host_table_wrong(9, ok) and M.host_table_wrong(10, ok) and M.host_table_wrong(8, ok) and not M.host_table_wrong(0, ok[:0])
-    for row, col, val in ((1, 0, 2), (1, 1, 0), (2, 1, 6), (0, 0, 1), (0, 1, -1)):
-        bad = ok.copy()
-        bad[row, col] = val
-        assert M.host_table_wrong(9, bad), (row, col, val)
 
 
 # ---- the model on its own: hand cases ----
