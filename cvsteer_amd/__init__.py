@@ -8,6 +8,7 @@ works anywhere the library loads, but creating a filter object needs a HIP devic
 from ._lib import CHAIN_CLOSED, CHAIN_HEAD_JUNCTION, CHAIN_TAIL_JUNCTION, CvsError, abi_version, lib, lib_path  # noqa: F401
 from ._lib import SEG_DEGENERATE, SEG_WRAPS  # noqa: F401
 from ._lib import TURN_CORNER, TURN_DEGENERATE, TURN_END, TURN_NO_CHAIN, TURN_SHORT  # noqa: F401
+from ._lib import MEMBER_REVERSED  # noqa: F401
 from ._lib import JOIN_CROWDED, JOIN_DEGENERATE, JOIN_MUTUAL, JOIN_NO_CHAIN, JOIN_NONE, JOIN_SHORT  # noqa: F401
 from .api import (  # noqa: F401
     SETUP_BASIS, SETUP_FULL, SETUP_ORIENT, SteerableFilters, SteerableFiltersG2, SteerableFiltersG4,
@@ -20,5 +21,5 @@ __all__ = [
     "SETUP_BASIS", "SETUP_ORIENT", "SETUP_FULL", "KIND_G2", "KIND_G4", "alloc_planes", "pyramid_setup",
     "CHAIN_CLOSED", "CHAIN_HEAD_JUNCTION", "CHAIN_TAIL_JUNCTION", "SEG_WRAPS", "SEG_DEGENERATE",
     "TURN_CORNER", "TURN_END", "TURN_DEGENERATE", "TURN_SHORT", "TURN_NO_CHAIN",
-    "JOIN_MUTUAL", "JOIN_NONE", "JOIN_CROWDED", "JOIN_SHORT", "JOIN_DEGENERATE", "JOIN_NO_CHAIN",
+    "MEMBER_REVERSED", "JOIN_MUTUAL", "JOIN_NONE", "JOIN_CROWDED", "JOIN_SHORT", "JOIN_DEGENERATE", "JOIN_NO_CHAIN",
 ]

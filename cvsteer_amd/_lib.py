@@ -101,6 +101,20 @@ class ChainJoin(C.Structure):
 
 
 JOIN_MUTUAL, JOIN_NONE, JOIN_CROWDED, JOIN_SHORT, JOIN_DEGENERATE, JOIN_NO_CHAIN = 1, 2, 4, 8, 16, 32
+
+
+class PathMember(C.Structure):
+    """struct cvs_path_member"""
+    _fields_ = [("chain", C.c_int32), ("flags", C.c_int32), ("path", C.c_int32), ("start", C.c_int32)]
+
+
+class PathInfo(C.Structure):
+    """struct cvs_path_info"""
+    _fields_ = [("first_member", C.c_int32), ("n_members", C.c_int32), ("first_end", C.c_int32), ("last_end", C.c_int32)]
+
+
+MEMBER_REVERSED = 1
+PATH_SCRATCH_PER_END = 80
 PEAKS_MAX = 4
 
 
@@ -164,6 +178,8 @@ SIGNATURES = {
     "cvs_chain_turns": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(TurnCfg), C.c_void_p, C.c_void_p,
                                   C.c_int]),
     "cvs_chain_joins": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(JoinCfg), C.c_void_p, C.c_int]),
+    "cvs_chain_paths": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "cvs_contour_chains_batch": (C.c_int, [C.c_void_p, C.c_int, _PP, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, _IP, _IP]),
     "cvs_chain_refine_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _PP, _PP, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_int]),

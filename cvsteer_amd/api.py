@@ -968,6 +968,91 @@ class _CallerPipeline:
         xy, _ = self.chain_refine(points, map, theta)
         return self.chain_joins(points, chains, xy=xy, **cfg), points, chains, xy
 
+    # -- contour paths (extension beyond the reference): cvs_chain_paths --
+    PATH_MEMBER_DTYPE = np.dtype([("chain", "<i4"), ("flags", "<i4"), ("path", "<i4"), ("start", "<i4")])
+    PATH_INFO_DTYPE = np.dtype([("first_member", "<i4"), ("n_members", "<i4"), ("first_end", "<i4"), ("last_end", "<i4")])
+
+    def chain_paths(self, points, chains, joins, xy=None, return_index=False, out=None):
+        """Stitch the chains into paths over their MUTUAL joins (cvs_chain_paths).  points (N, 2) int32 and chains (M, 4) int32 as
+        contour_chains or contour_chains_batch return them, joins as chain_joins returns it (the structured array) or as its out= tensor
+        ((2M, 32) uint8), xy (N, 2) float32 as chain_refine does.  Returns (path_points, paths, members, info[, path_xy][, index]) trimmed
+        to the counts: path_points (P, 2) int32 and paths (K, 4) int32 are again a (points, chains) pair -- path p is
+        path_points[start:start + length], flags CHAIN_CLOSED for a cycle -- that every chain call takes as it is; members (structured,
+        PATH_MEMBER_DTYPE: chain, flags & MEMBER_REVERSED, path, start) lists the chains of every path in walk order, info (structured,
+        PATH_INFO_DTYPE) says which members a path has and through which ends it starts and leaves; path_xy (with xy) holds the refined
+        position and index (return_index=True) the position in `points` of every path point.  Torch CUDA arrays take the device path:
+        the launches read nothing back, and the eight bytes of the counts are read here, afterwards, to trim; path_points, paths, path_xy
+        and index stay tensors on the device, members and info are downloaded.  With out= a tuple of full-size CUDA tensors
+        (path_points (N, 2) int32, paths (M, 4) int32, members (M, 16) uint8, info (M, 16) uint8[, path_xy (N, 2) float32][, index (N,)
+        int32], counts (2,) int32) nothing is read back at all (capturable once the handle's scratch has its size): `out` is returned
+        untrimmed, counts says how much of each tensor holds a result.  numpy arrays and torch CPU tensors take the host path.
+        include/cvsteer_hip.h has the contract."""
+        dev = _is_torch(points) and points.is_cuda
+        back = _is_torch(points) and not dev
+        points = self._chain_array(points, dev, np.int32, 2, "points")
+        chains = self._chain_array(chains, dev, np.int32, 4, "chains")
+        xy = self._chain_array(xy, dev, np.float32, 2, "xy")
+        n, m = int(points.shape[0]), int(chains.shape[0])
+        if isinstance(joins, np.ndarray) and joins.dtype.names:
+            joins = np.ascontiguousarray(joins).view(np.uint8).reshape(-1, self.JOIN_DTYPE.itemsize)
+            if dev:
+                joins = torch.from_numpy(joins).to(points.device)
+        joins = self._chain_array(joins, dev, np.uint8, self.JOIN_DTYPE.itemsize, "joins")
+        if joins.shape[0] != 2 * m:
+            raise ValueError("joins: two records per chain")
+        if xy is not None and xy.shape[0] != n:
+            raise ValueError("xy: one entry per point")
+        shapes = [(np.int32, (n, 2)), (np.int32, (m, 4)), (np.uint8, (m, 16)), (np.uint8, (m, 16))]
+        shapes += [(np.float32, (n, 2))] if xy is not None else []
+        shapes += [(np.int32, (n,))] if return_index else []
+        shapes += [(np.int32, (2,))]
+        if out is not None:
+            bufs = list(out)
+            if not (dev and len(bufs) == len(shapes) and all(self._is_out(b, dev, dt, sh) for b, (dt, sh) in zip(bufs, shapes))):
+                raise ValueError("out: contiguous CUDA tensors (path_points (N, 2) int32, paths (M, 4) int32, members (M, 16) uint8, info "
+                                 "(M, 16) uint8[, path_xy (N, 2) float32][, index (N,) int32], counts (2,) int32), with device arrays")
+        elif dev:
+            bufs = [torch.empty(sh, dtype=getattr(torch, np.dtype(dt).name), device=points.device) for dt, sh in shapes]
+        else:
+            bufs = [np.zeros(sh, dt) for dt, sh in shapes]
+        if dev:
+            self._bind_stream(points)
+        it = iter(bufs)
+        path_points, paths, members, info = next(it), next(it), next(it), next(it)
+        path_xy = next(it) if xy is not None else None
+        index = next(it) if return_index else None
+        counts = next(it)
+        p = self._array_ptr
+        self._check(lib().cvs_chain_paths(self._h, p(points), n, p(chains), m, p(joins), p(xy), p(path_points), p(paths), p(info), p(members),
+                                          p(index), p(path_xy), p(counts), L.MEM_DEVICE if dev else L.MEM_HOST), "cvs_chain_paths")
+        if out is not None:
+            return out
+        k, q = (int(v) for v in (counts.cpu() if dev else counts).tolist())   # (device path: the one read-back, after the call)
+        q = min(q, n)
+        host = (lambda t: t.cpu().numpy()) if dev else (lambda t: t)
+        info = host(info[:k]).view(self.PATH_INFO_DTYPE).reshape(-1)
+        n_members = int(info["n_members"].sum())                              # (every valid chain is one member)
+        r = [path_points[:q], paths[:k], host(members[:n_members]).view(self.PATH_MEMBER_DTYPE).reshape(-1), info]
+        r += [path_xy[:q]] if xy is not None else []
+        r += [index[:q]] if return_index else []
+        if back:
+            r = [torch.from_numpy(np.ascontiguousarray(t)) if i not in (2, 3) else t for i, t in enumerate(r)]
+        return tuple(r)
+
+    def contour_paths(self, mask, map, theta=None, **cfg):
+        """The whole contours of a mask: contour_chains(mask) -> chain_refine on the un-thinned `map` the mask came from -> chain_joins on
+        the refined positions (**cfg: its radius, min_arm and min_cos) -> chain_paths.  Returns (path_points, paths, members, info,
+        path_xy): what chain_paths returns with xy."""
+        points, chains = self.contour_chains(mask)
+        xy, _ = self.chain_refine(points, map, theta)
+        dev = _is_torch(points) and points.is_cuda
+        if dev:
+            table = torch.empty((2 * int(chains.shape[0]), self.JOIN_DTYPE.itemsize), dtype=torch.uint8, device=points.device)
+            joins = self.chain_joins(points, chains, xy=xy, out=table, **cfg)   # (stays on the device)
+        else:
+            joins = self.chain_joins(points, chains, xy=xy, **cfg)
+        return self.chain_paths(points, chains, joins, xy=xy)
+
     def contours(self, image, low, high, min_area=0, min_peak=0.0):
         """Thin, linked contours of one image: pipeline(image) -> nonmax(edges, dark, bright) on the object's own theta ->
         hysteresis(low, high).  Returns three uint8 masks (edges, dark lines, bright lines).  min_area > 0 or min_peak > 0: the

@@ -327,6 +327,58 @@ int join_contours(cvs_handle h, const Mat1f& response, const std::vector<std::ve
     return CVS_OK;
 }
 
+// cvs_chain_paths on host arrays: the chains packed as for the joins, a join table that holds nothing but the partners of the mutual joins
+// (what joinContours returned), and the paths, their flags and their member lists unpacked from the records
+int stitch_contours(cvs_handle h, const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags, const std::vector<int>& partners,
+                    std::vector<std::vector<Point> >& paths, std::vector<int>* pathFlags, std::vector<std::vector<int> >* members, int* n)
+{
+    if ((flags && flags->size() != chains.size()) || partners.size() != 2 * chains.size()) return CVS_E_BADARG;
+    size_t np = 0;
+    for (size_t c = 0; c < chains.size(); ++c) np += chains[c].size();
+    if (np > (size_t)1 << 30 || chains.size() > (size_t)1 << 26) return CVS_E_SIZE;
+    std::vector<int32_t> pts(np * 2), out(np * 2);
+    std::vector<cvs_chain> tab(chains.size()), ptab(chains.size());
+    std::vector<cvs_chain_join> joins(2 * chains.size());
+    std::vector<cvs_path_info> info(chains.size());
+    std::vector<cvs_path_member> mem(chains.size());
+    size_t at = 0;
+    for (size_t c = 0; c < chains.size(); ++c) {
+        tab[c].start = (int32_t)at;
+        tab[c].length = (int32_t)chains[c].size();
+        tab[c].flags = flags ? (*flags)[c] : 0;
+        tab[c].reserved = 0;
+        for (size_t k = 0; k < chains[c].size(); ++k, ++at) {
+            pts[2 * at] = chains[c][k].x;
+            pts[2 * at + 1] = chains[c][k].y;
+        }
+    }
+    for (size_t e = 0; e < joins.size(); ++e) {
+        cvs_chain_join j = cvs_chain_join();
+        j.node = j.next = -1;
+        j.partner = partners[e];
+        j.flags = partners[e] >= 0 ? CVS_JOIN_MUTUAL : CVS_JOIN_NONE;
+        j.cos = j.sin = std::numeric_limits<float>::quiet_NaN();
+        joins[e] = j;
+    }
+    int32_t counts[2] = {0, 0};
+    const int rc = cvs_chain_paths(h, pts.data(), (int)np, tab.data(), (int)chains.size(), joins.data(), 0, out.data(), ptab.data(), info.data(),
+                                   mem.data(), 0, 0, counts, CVS_MEM_HOST);
+    if (rc != CVS_OK) return rc;
+    paths.assign((size_t)counts[0], std::vector<Point>());
+    if (pathFlags) pathFlags->assign((size_t)counts[0], 0);
+    if (members) members->assign((size_t)counts[0], std::vector<int>());
+    for (size_t p = 0; p < (size_t)counts[0]; ++p) {
+        paths[p].reserve((size_t)ptab[p].length);
+        for (int32_t k = ptab[p].start; k < ptab[p].start + ptab[p].length; ++k) paths[p].push_back(Point(out[2 * (size_t)k], out[2 * (size_t)k + 1]));
+        if (pathFlags) (*pathFlags)[p] = ptab[p].flags;
+        if (members)
+            for (int32_t m = info[p].first_member; m < info[p].first_member + info[p].n_members; ++m)
+                (*members)[p].push_back(2 * mem[(size_t)m].chain + ((mem[(size_t)m].flags & CVS_MEMBER_REVERSED) ? 1 : 0));
+    }
+    *n = counts[0];
+    return CVS_OK;
+}
+
 }  // namespace
 
 // --------------------------------------------------------------------------- base
@@ -619,6 +671,14 @@ int SteerableFiltersG2::joinContours(const Mat1f& response, const std::vector<st
     return n;
 }
 
+int SteerableFiltersG2::stitchContours(const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags, const std::vector<int>& partners,
+                                       std::vector<std::vector<Point> >& paths, std::vector<int>* pathFlags, std::vector<std::vector<int> >* members)
+{
+    int n = 0;
+    check(stitch_contours(m_handle, chains, flags, partners, paths, pathFlags, members, &n), "cvs_chain_paths");
+    return n;
+}
+
 void SteerableFiltersG2::phaseWeights(const Mat1f& phase, Mat1f& lambda, float phi, bool signum, float k)
 {
     std::lock_guard<std::mutex> lock(g_static_mutex);
@@ -802,6 +862,14 @@ int SteerableFiltersG4::joinContours(const Mat1f& response, const std::vector<st
 {
     int n = 0;
     check(join_contours(m_handle, response, chains, flags, radius, minCosine, partners, cosines, &n), "cvs_chain_joins");
+    return n;
+}
+
+int SteerableFiltersG4::stitchContours(const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags, const std::vector<int>& partners,
+                                       std::vector<std::vector<Point> >& paths, std::vector<int>* pathFlags, std::vector<std::vector<int> >* members)
+{
+    int n = 0;
+    check(stitch_contours(m_handle, chains, flags, partners, paths, pathFlags, members, &n), "cvs_chain_paths");
     return n;
 }
 

@@ -59,6 +59,14 @@ public:
     // where the object has no orientation state)
     int joinContours(const Mat1f& response, const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags, int radius,
                      float minCosine, std::vector<int>& partners, std::vector<float>* cosines = 0);
+    // contour paths (extension, cvs_chain_paths): the chains stitched into whole contours over the mutual joins -- chains, flags and
+    // `partners` as joinContours took and returned them (2 entries per chain; -1: no mutual join).  paths[p] = the points of path p: its
+    // chains in walk order, a chain entered through its tail listed backwards, the junction pixel between two chains listed once, and a
+    // path that closes on itself without its first pixel repeated; pathFlags (optional): CVS_CHAIN_CLOSED for such a cycle or a closed
+    // chain, else the junction bits of the path's two ends; members (optional): members[p] = 2 * chain + reversed for every chain of path
+    // p, in walk order.  Paths are ordered by the contract of include/cvsteer_hip.h.  Returns the number of paths
+    int stitchContours(const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags, const std::vector<int>& partners,
+                       std::vector<std::vector<Point> >& paths, std::vector<int>* pathFlags = 0, std::vector<std::vector<int> >* members = 0);
 
 protected:
     // the reference's protected members, same names (SteerableFiltersG4.h:50-56): 11 tap vectors; the planes m_g4a..m_h4f

@@ -682,7 +682,7 @@ int cvs_chain_turns(cvs_handle h, const int32_t* points, int n_points, const cvs
 /* EXTENSION: contour joins -- what cvs_contour_chains took away when it cut the contours at their junctions: table[2c] and table[2c+1]
  * say which other chain ends lie at the same node as the head and the tail of chain c, and which of them continues the chain most nearly
  * straight.  One fixed-size record per chain END, so the table lines up with `chains`: no count, no prefix sum, nothing read back.  Needs
- * no image size (any handle, before or after a setup).  Stitching chains into paths over the joins is left to the caller.
+ * no image size (any handle, before or after a setup).  Stitching chains into paths over the MUTUAL joins is cvs_chain_paths, below.
  * ENDS.  Chain c = (S, L, F, R) = chains[c].  Its head, end 2c, sits at position j = S and its arm runs forwards (sign +1); its tail, end
  * 2c+1, sits at j = S+L-1 and its arm runs backwards (sign -1).  A chain with CVS_CHAIN_CLOSED or with L < 2 has no ends: both its
  * records are node = next = partner = -1, degree = n = 0, cos = sin = NaN, flags = CVS_JOIN_NONE.  Every NaN the call stores is the quiet
@@ -752,6 +752,79 @@ int cvs_chain_joins(cvs_handle h, const int32_t* points, int n_points, const cvs
                     const float* xy,            /* NULL: the integer points */
                     const cvs_join_cfg* cfg,
                     cvs_chain_join* table,      /* 2 * n_chains records */
+                    int mem);
+
+/* EXTENSION: contour paths -- the chains of a chain table put back together over the MUTUAL joins of cvs_chain_joins: (points, chains,
+ * joins) becomes (path_points, paths), and `paths` is again a chain table that obeys the running-sum rule, so every chain-array call
+ * (cvs_chain_polylines, cvs_chain_measures, cvs_polyline_segments, cvs_chain_turns, cvs_chain_joins itself) runs on whole contours as
+ * it is.  All outputs are sized by the inputs: no sizing call, no capacity, nothing read back.  Integer arithmetic only; coordinates are
+ * copied, never compared.  Needs no image size.
+ * ENTRIES, ENDS, LINKS.  Entry c = (S, L, F, R) = chains[c] is VALID iff S >= 0, L >= 1 and S + L <= n_points.  A valid entry HAS ENDS
+ * iff L >= 2 and CVS_CHAIN_CLOSED is not set: end 2c is its head (position S), end 2c+1 its tail (position S+L-1).  End e is LINKED iff,
+ * with p = joins[e].partner: chain e>>1 has ends, joins[e].flags has CVS_JOIN_MUTUAL, 0 <= p < 2 n_chains, p != e, chain p>>1 has ends,
+ * joins[p].flags has CVS_JOIN_MUTUAL and joins[p].partner == e.  The test is symmetric, so the linked ends are paired off whatever bytes
+ * the join table holds; p == e^1 is allowed (a loop whose two ends continue each other).  No other field of a join record is read.
+ * WALKS.  Entering a chain through end e lists its positions from e's position to the other end's: even e gives S .. S+L-1, odd e gives
+ * S+L-1 .. S.  succ(e) = joins[e^1].partner if LINKED(e^1), else none: out through the other end, into its partner.  Every end has at
+ * most one successor and one predecessor, so the entry ends form disjoint lists and cycles.  Every path appears as two TWIN walks, each
+ * the other reversed with every e replaced by e^1; twins are never the same walk.
+ * CANONICAL WALK.  Open path: the twin whose first entry end is the smaller number.  Cycle: the twin that contains the smallest end
+ * number of the two, started at that end (always a head, so that chain goes forward).  A valid entry without ends is a path of one
+ * member, entry end 2c, not reversed.  An invalid entry (DEVICE memory only) makes no path, no member and no point.  Paths are sorted
+ * ascending by their first entry end; the members of a path are in walk order.
+ * POINTS.  Member k >= 1 drops its first position (the junction pixel the member before it listed); a cycle also drops the last
+ * position of its last member; the rest go, in order, into path_points, and where given into index (the position in `points`) and
+ * path_xy (the bits of xy).  A member may emit no point at all (a cycle's last member with L = 2).
+ * RECORDS.  paths[p] = (start, length, flags, R of the first member's chain): the starts are the running sum of the lengths; flags is
+ * CVS_CHAIN_CLOSED for a cycle or a closed member, else CVS_CHAIN_HEAD_JUNCTION from the junction bit of the first entry end (entering
+ * through a head reads the chain's HEAD_JUNCTION, through a tail its TAIL_JUNCTION) and CVS_CHAIN_TAIL_JUNCTION likewise from the last
+ * member's exit end.  info[p] = (first member, number of members, first entry end, exit end of the last member).  members[m] = (chain,
+ * CVS_MEMBER_REVERSED iff entered through the tail, path, index in path_points of its first emitted point -- where that point would be
+ * if it emits none).  counts = (n_paths, n_path_points); records and points past the counts are not written.
+ * IT FOLLOWS that n_path_points = (points of valid entries) - (linked pairs), n_paths = (valid entries) - (linked pairs) + (cycles),
+ * members = valid entries; and that with no linked end and a table that obeys the running-sum rule the outputs are the inputs: paths
+ * == chains byte for byte (for flags the library writes), path_points == points, index = 0 .. n-1, members[c] = (c, 0, c, S).
+ * MEMORY.  All arrays are in host or all in device memory (mem).  HOST: `chains` is checked in full -- CVS_E_BADARG unless the starts are
+ * the running sum of the lengths from 0 to n_points and every length is >= 1 (the join table needs no check: LINKED is total); the
+ * arrays are staged in handle scratch, the call synchronises, and it returns CVS_E_UNSUPPORTED while the stream is being captured.
+ * DEVICE: tables are trusted for nothing -- every index is checked before it is an address, no load and no store leaves the arrays;
+ * entries may overlap or leave gaps, and where overlapping valid entries add up to more than n_points points the sums (starts, lengths,
+ * counts) are formed modulo 2^32 and points at an index >= n_points are not stored.
+ * EXECUTION.  One lane per end: links, pointer jumping over the walks between two buffers (first along succ for each walk's last and
+ * smallest end, then, with every cycle cut in front of its smallest end, along pred for each member's rank and point offset), a scan
+ * over the ends that numbers the paths and sums their lengths and members, the records, the points.  2 * ceil(log2(n_chains)) + 8
+ * launches (8 for n_chains == 1), a function of n_chains alone -- a table of arbitrary bytes takes the same launches as a good one; no
+ * kernel has a loop without a static bound, none waits or spins, none uses an atomic.  Queued on the handle's stream, nothing read
+ * back, nothing synchronised, capturable.  The same call twice gives the same bytes.  Handle scratch (grown only, freed by cvs_destroy):
+ * CVS_PATH_SCRATCH_PER_END = 80 bytes per end, 160 per chain, and 12 bytes per 1024 ends.  A call that would have to GROW the scratch
+ * while the stream is being captured returns CVS_E_UNSUPPORTED ("call once eagerly first", the rule of cvs_chain_joins); the handle
+ * works on.  n_chains == 0: counts = (0, 0), CVS_OK.
+ * CVS_E_BADARG, nothing written: a negative count; a required array missing (counts; points / path_points with n_points > 0; chains /
+ * joins / paths / info / members with n_chains > 0); path_xy without xy or xy without path_xy; n_points > 0 with n_chains == 0; an
+ * invalid mem; a pointer not aligned to 4 bytes; an output overlapping an input or another output; a HOST table as above.  n_points >
+ * 2^30 or n_chains > 2^26: CVS_E_SIZE. */
+typedef struct cvs_path_member {     /* 16 bytes, one per valid chain, in path and walk order */
+    int32_t chain;
+    int32_t flags;                   /* CVS_MEMBER_REVERSED = 1: entered through its tail, its points run backwards */
+    int32_t path;
+    int32_t start;                   /* index in path_points of its first emitted point */
+} cvs_path_member;
+typedef struct cvs_path_info {       /* 16 bytes, one per path */
+    int32_t first_member, n_members; /* members[first_member .. first_member + n_members) */
+    int32_t first_end, last_end;     /* the first member's entry end, the last member's exit end */
+} cvs_path_info;
+enum { CVS_MEMBER_REVERSED = 1 };
+enum { CVS_PATH_SCRATCH_PER_END = 80 };
+int cvs_chain_paths(cvs_handle h, const int32_t* points, int n_points, const cvs_chain* chains, int n_chains,
+                    const cvs_chain_join* joins,      /* 2 * n_chains records, as cvs_chain_joins writes them */
+                    const float* xy,                  /* NULL, or n_points (xs, ys) pairs */
+                    int32_t* path_points,             /* room for n_points (x, y) pairs */
+                    cvs_chain* paths,                 /* room for n_chains entries */
+                    cvs_path_info* info,              /* room for n_chains records */
+                    cvs_path_member* members,         /* room for n_chains records */
+                    int32_t* index,                   /* NULL, or room for n_points: path point k is points[index[k]] */
+                    float* path_xy,                   /* required iff xy != NULL: room for n_points pairs */
+                    int32_t* counts,                  /* 2 ints, same mem: n_paths, n_path_points */
                     int mem);
 
 /* ---- EXTENSION beyond the reference: the contour chain on the batch axis -- cvs_link, cvs_nonmax_batch, cvs_contours_batch ----
