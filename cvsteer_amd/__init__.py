@@ -10,6 +10,10 @@ from ._lib import SEG_DEGENERATE, SEG_WRAPS  # noqa: F401
 from ._lib import TURN_CORNER, TURN_DEGENERATE, TURN_END, TURN_NO_CHAIN, TURN_SHORT  # noqa: F401
 from ._lib import MEMBER_REVERSED  # noqa: F401
 from ._lib import JOIN_CROWDED, JOIN_DEGENERATE, JOIN_MUTUAL, JOIN_NO_CHAIN, JOIN_NONE, JOIN_SHORT  # noqa: F401
+from ._lib import (  # noqa: F401
+    BRIDGE_CROWDED, BRIDGE_DEGENERATE, BRIDGE_JUNCTION, BRIDGE_MUTUAL, BRIDGE_NO_CHAIN, BRIDGE_NONE, BRIDGE_SHORT,
+)
+from .api import BRIDGE_DTYPE  # noqa: F401
 from .api import (  # noqa: F401
     SETUP_BASIS, SETUP_FULL, SETUP_ORIENT, SteerableFilters, SteerableFiltersG2, SteerableFiltersG4,
     KIND_G2, KIND_G4, alloc_planes, basis_taps, make_taps, num_basis, pyramid_setup, steer_weights,
@@ -22,4 +26,5 @@ __all__ = [
     "CHAIN_CLOSED", "CHAIN_HEAD_JUNCTION", "CHAIN_TAIL_JUNCTION", "SEG_WRAPS", "SEG_DEGENERATE",
     "TURN_CORNER", "TURN_END", "TURN_DEGENERATE", "TURN_SHORT", "TURN_NO_CHAIN",
     "MEMBER_REVERSED", "JOIN_MUTUAL", "JOIN_NONE", "JOIN_CROWDED", "JOIN_SHORT", "JOIN_DEGENERATE", "JOIN_NO_CHAIN",
+    "BRIDGE_MUTUAL", "BRIDGE_NONE", "BRIDGE_JUNCTION", "BRIDGE_SHORT", "BRIDGE_DEGENERATE", "BRIDGE_NO_CHAIN", "BRIDGE_CROWDED", "BRIDGE_DTYPE",
 ]

@@ -115,6 +115,21 @@ class PathInfo(C.Structure):
 
 MEMBER_REVERSED = 1
 PATH_SCRATCH_PER_END = 80
+
+
+class BridgeCfg(C.Structure):
+    """struct cvs_bridge_cfg"""
+    _fields_ = [("radius", C.c_int32), ("min_arm", C.c_int32), ("max_gap", C.c_int32), ("min_cos", C.c_float)]
+
+
+class ChainBridge(C.Structure):
+    """struct cvs_chain_bridge"""
+    _fields_ = [("partner", C.c_int32), ("flags", C.c_int32), ("n", C.c_int32), ("steps", C.c_int32), ("bridge", C.c_int32), ("start", C.c_int32),
+                ("cos", C.c_float), ("cos_partner", C.c_float)]
+
+
+BRIDGE_MUTUAL, BRIDGE_NONE, BRIDGE_JUNCTION, BRIDGE_SHORT, BRIDGE_DEGENERATE, BRIDGE_NO_CHAIN, BRIDGE_CROWDED = 1, 2, 4, 8, 16, 32, 64
+BRIDGE_SCRATCH_PER_CHAIN, BRIDGE_MAX_GAP, BRIDGE_MAX_CELL = 244, 32, 32
 PEAKS_MAX = 4
 
 
@@ -180,6 +195,8 @@ SIGNATURES = {
     "cvs_chain_joins": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(JoinCfg), C.c_void_p, C.c_int]),
     "cvs_chain_paths": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "cvs_chain_bridges": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(BridgeCfg), C.c_void_p, C.c_void_p,
+                                    C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
     "cvs_contour_chains_batch": (C.c_int, [C.c_void_p, C.c_int, _PP, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, _IP, _IP]),
     "cvs_chain_refine_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _PP, _PP, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_int]),

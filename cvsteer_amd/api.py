@@ -37,6 +37,9 @@ def _is_torch(a):
 
 KIND_G2, KIND_G4 = L.KIND_G2, L.KIND_G4
 CHAIN_CLOSED, CHAIN_HEAD_JUNCTION, CHAIN_TAIL_JUNCTION = L.CHAIN_CLOSED, L.CHAIN_HEAD_JUNCTION, L.CHAIN_TAIL_JUNCTION
+# numpy mirror of `struct cvs_chain_bridge`: one record per chain end
+BRIDGE_DTYPE = np.dtype([("partner", "<i4"), ("flags", "<i4"), ("n", "<i4"), ("steps", "<i4"), ("bridge", "<i4"), ("start", "<i4"), ("cos", "<f4"),
+                         ("cos_partner", "<f4")])
 
 
 def alloc_planes(n, rows, cols, device=None):
@@ -1052,6 +1055,115 @@ class _CallerPipeline:
         else:
             joins = self.chain_joins(points, chains, xy=xy, **cfg)
         return self.chain_paths(points, chains, joins, xy=xy)
+
+    # -- contour bridges (extension beyond the reference): cvs_chain_bridges --
+    BRIDGE_DTYPE = BRIDGE_DTYPE
+
+    def chain_bridges(self, points, chains, xy=None, radius=8, min_arm=3, max_gap=8, min_cos=0.8, emit=True, capacity=None, out=None):
+        """Bridge the gaps between free chain ends that face each other (cvs_chain_bridges).  points (N, 2) int32 and chains (M, 4) int32
+        as contour_chains, contour_chains_batch or chain_paths return them, xy (N, 2) float32 as chain_refine does: xy=None takes the
+        integer points.  Two free ends are paired when their pixels are 2 .. max_gap apart (Chebyshev), each points at the other within
+        the cone min_cos -- judged on arms of up to `radius` points, at least min_arm -- and each is the other's nearest such end.
+        Returns (bridges, out_points, out_chains, out_xy): bridges a numpy structured array (BRIDGE_DTYPE: partner, flags & BRIDGE_*, n,
+        steps, bridge, start, cos, cos_partner), two records per chain; out_points (N + B, 2) int32 and out_chains (M + K, 4) int32 the
+        inputs with every bridge appended as a chain of its own (a digital line from the one end pixel to the other, flags
+        CHAIN_HEAD_JUNCTION | CHAIN_TAIL_JUNCTION) and the junction bit of every bridged end set: again a (points, chains) pair, on
+        which chain_joins and chain_paths stitch through the bridges; out_xy (N + B, 2) float32 with xy, else None.  emit=False: the
+        table alone, (bridges, None, None, None).  Torch CUDA arrays take the device path and give tensors on their device (bridges is
+        downloaded).  capacity=None calls twice: once for the table and the counts, whose twelve bytes are then read back -- the ONE
+        read-back -- and once more with arrays of exactly that size.  capacity=(points, chains) calls once with arrays of that size and
+        returns what fitted of the bridges, a prefix.  out= a tuple of the caller's own CUDA tensors (bridges (2M, 32) uint8, out_points
+        (P, 2) int32, out_chains (K, 4) int32[, out_xy (P, 2) float32 with xy], counts (3,) int32), P >= N and K >= M the capacities:
+        one call, nothing read back at all (capturable once the handle's scratch has its size); `out` is returned, counts = (bridges,
+        chains, points) in full whatever fitted.  numpy arrays and torch CPU tensors take the host path.  include/cvsteer_hip.h has the
+        contract."""
+        dev = _is_torch(points) and points.is_cuda
+        back = _is_torch(points) and not dev
+        points = self._chain_array(points, dev, np.int32, 2, "points")
+        chains = self._chain_array(chains, dev, np.int32, 4, "chains")
+        xy = self._chain_array(xy, dev, np.float32, 2, "xy")
+        n, m = int(points.shape[0]), int(chains.shape[0])
+        if xy is not None and xy.shape[0] != n:
+            raise ValueError("xy: one entry per point")
+        cfg = L.BridgeCfg(int(radius), int(min_arm), int(max_gap), float(min_cos))
+        size = BRIDGE_DTYPE.itemsize
+        p = self._array_ptr
+        if dev:
+            self._bind_stream(points)
+            new = lambda shape, dt: torch.empty(shape, dtype=getattr(torch, np.dtype(dt).name), device=points.device)
+        else:
+            new = lambda shape, dt: np.zeros(shape, dt)
+
+        def call(table, o_pts, cap_p, o_chn, cap_c, o_xy, counts):
+            self._check(lib().cvs_chain_bridges(self._h, p(points), n, p(chains), m, p(xy), C.byref(cfg), p(table), p(o_pts), cap_p, p(o_chn), cap_c,
+                                                p(o_xy), p(counts), L.MEM_DEVICE if dev else L.MEM_HOST), "cvs_chain_bridges")
+
+        if out is not None:
+            bufs = list(out)
+            ok = dev and len(bufs) == (5 if xy is not None else 4) and all(_is_torch(b) and b.is_cuda and b.ndim >= 1 for b in bufs)
+            if ok:
+                cap_p, cap_c = int(bufs[1].shape[0]), int(bufs[2].shape[0])
+                shapes = [(np.uint8, (2 * m, size)), (np.int32, (cap_p, 2)), (np.int32, (cap_c, 4))]
+                shapes += [(np.float32, (cap_p, 2))] if xy is not None else []
+                shapes += [(np.int32, (3,))]
+                ok = cap_p >= max(n, 1) and cap_c >= max(m, 1) and all(self._is_out(b, dev, dt, sh) for b, (dt, sh) in zip(bufs, shapes))
+            if not ok:
+                raise ValueError("out: contiguous CUDA tensors (bridges (2 M, %d) uint8, out_points (P, 2) int32, out_chains (K, 4) int32[, out_xy "
+                                 "(P, 2) float32], counts (3,) int32) with P >= N and K >= M, with device arrays" % size)
+            call(bufs[0], bufs[1], cap_p, bufs[2], cap_c, bufs[3] if xy is not None else None, bufs[-1])
+            return out
+        table, counts = new((2 * m, size), np.uint8), new((3,), np.int32)
+        records = lambda: (table.cpu().numpy() if dev else table).view(BRIDGE_DTYPE).reshape(-1)
+        if not emit:
+            call(table, None, 0, None, 0, None, counts)
+            return records(), None, None, None
+        if capacity is None:
+            call(table, None, 0, None, 0, None, counts)
+            _, cap_c, cap_p = (int(v) for v in (counts.cpu() if dev else counts).tolist())   # (device path: the one read-back)
+            if cap_p < n:
+                raise ValueError("more than 2^31 - 1 output points")
+        else:
+            cap_p, cap_c = (int(v) for v in capacity)
+            if cap_p < n or cap_c < m:
+                raise ValueError("capacity: (points, chains), at least the inputs")
+        o_pts, o_chn = new((max(cap_p, 1), 2), np.int32), new((max(cap_c, 1), 4), np.int32)
+        o_xy = None if xy is None else new((max(cap_p, 1), 2), np.float32)
+        call(table, o_pts, cap_p, o_chn, cap_c, o_xy, counts)
+        rec = records()
+        if capacity is None:
+            k, q = cap_c, cap_p
+        else:                                                                                # what fitted: a prefix of the bridges
+            b = rec[(rec["bridge"] >= 0) & (np.arange(len(rec)) < rec["partner"])]
+            last = b["start"].astype(np.int64) + b["steps"]
+            fits = (m + b["bridge"].astype(np.int64) < cap_c) & (b["start"] >= 0) & (last < cap_p)
+            k = m + int(fits.sum())
+            q = int(last[fits].max()) + 1 if fits.any() else n
+        r = [o_pts[:q], o_chn[:k], None if o_xy is None else o_xy[:q]]
+        if back:
+            r = [None if t is None else torch.from_numpy(np.ascontiguousarray(t)) for t in r]
+        return (rec,) + tuple(r)
+
+    def contour_bridges(self, mask, map=None, theta=None, radius=8, min_arm=3, join_min_cos=-1.0, max_gap=8, min_cos=0.8):
+        """The whole contours of a mask with their gaps bridged: contour_chains(mask) [-> chain_refine on the un-thinned `map` the mask
+        came from, when given] -> chain_joins -> chain_paths -> chain_bridges on the paths -> chain_joins -> chain_paths.  radius and
+        min_arm are those of both chain_joins and of chain_bridges, join_min_cos the min_cos of the joins, max_gap and min_cos those of
+        the bridges.  The second chain_joins takes min(min_arm, 2), so that the shortest bridge -- three points, an arm of two -- is
+        eligible.  Returns what the last chain_paths returns: (path_points, paths, members, info[, path_xy with map]); `members` names
+        chains of the bridged table (the first pass's paths, then the bridges)."""
+        points, chains = self.contour_chains(mask)
+        xy = None if map is None else self.chain_refine(points, map, theta)[0]
+        def stitch(points, chains, xy, arm):
+            if _is_torch(points) and points.is_cuda:
+                table = torch.empty((2 * int(chains.shape[0]), self.JOIN_DTYPE.itemsize), dtype=torch.uint8, device=points.device)
+                joins = self.chain_joins(points, chains, xy=xy, radius=radius, min_arm=arm, min_cos=join_min_cos, out=table)   # (stays there)
+            else:
+                joins = self.chain_joins(points, chains, xy=xy, radius=radius, min_arm=arm, min_cos=join_min_cos)
+            return self.chain_paths(points, chains, joins, xy=xy)
+
+        r = stitch(points, chains, xy, int(min_arm))
+        _, points, chains, xy = self.chain_bridges(r[0], r[1], xy=None if xy is None else r[4], radius=radius, min_arm=min_arm, max_gap=max_gap,
+                                                   min_cos=min_cos)
+        return stitch(points, chains, xy, min(int(min_arm), 2))
 
     def contours(self, image, low, high, min_area=0, min_peak=0.0):
         """Thin, linked contours of one image: pipeline(image) -> nonmax(edges, dark, bright) on the object's own theta ->

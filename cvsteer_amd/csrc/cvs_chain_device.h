@@ -1,5 +1,5 @@
 // cvs_chain_device.h -- how the kernels of the contour tail read the arrays of a chain call (cvs_kernels_polyline.hip, _refine, _segments,
-// _turns, _joins, and the point pairs of cvs_kernels_chains_batch.hip): the 8-byte point pair, the entry of a chain table with the test that
+// _turns, _joins, _bridges, and the point pairs of cvs_kernels_chains_batch.hip): the 8-byte point pair, the entry of a chain table with the test that
 // it lies inside `points`, the search for the entry a position belongs to, and the loop of the workgroup kernels over the long entries.
 // Only the reading and the test are shared: what a kernel stores for a broken entry -- an empty record, NO_CHAIN, a chain of no points --
 // is its own.  Everything is __forceinline__ and returns by value, so a field a kernel does not use (the plane word, mostly) is never loaded.

@@ -1,5 +1,5 @@
 // cvs_chain_table.h -- what a HOST chain table is refused for, for every call of the contour tail that takes one (cvs_polyline.cpp,
-// cvs_refine.cpp, cvs_segments.cpp, cvs_turns.cpp, cvs_joins.cpp, cvs_paths.cpp), and the size of the join scratch, which cvs_joins.cpp and the join
+// cvs_refine.cpp, cvs_segments.cpp, cvs_turns.cpp, cvs_joins.cpp, cvs_paths.cpp, cvs_bridges.cpp), and the size of the join scratch, which cvs_joins.cpp and the join
 // kernels both compute.  A table is n_chains entries of four int32 words (start, length, flags, plane: struct cvs_chain).
 // No HIP header and no other header of the engine: tests/cpp/chain_table_san.cpp compiles this file alone under the host sanitizers.
 #pragma once
@@ -22,7 +22,7 @@ inline const char* chain_table_outside(int n_points, const int32_t* chains, int 
     return what;
 }
 
-// the running-sum rule (turns, joins, paths): the starts are the running sum of the lengths from 0 to n_points and every length is >= 1
+// the running-sum rule (turns, joins, paths, bridges): the starts are the running sum of the lengths from 0 to n_points and every length is >= 1
 inline const char* chain_table_not_running_sum(int n_points, const int32_t* chains, int n_chains)
 {
     long long at = 0;

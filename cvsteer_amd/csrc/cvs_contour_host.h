@@ -1,6 +1,6 @@
 // cvs_contour_host.h -- what the host units of the contour tail share in front of their kernels (cvs_contour.cpp, which defines it,
 // cvs_components.cpp, cvs_link.cpp, cvs_chains.cpp, cvs_chains_batch.cpp, cvs_polyline.cpp, cvs_refine.cpp, cvs_segments.cpp, cvs_turns.cpp,
-// cvs_joins.cpp, cvs_paths.cpp): the checks every entry point begins with, the handle's scratch as a bump allocator, the routes of mask inputs and mask
+// cvs_joins.cpp, cvs_paths.cpp, cvs_bridges.cpp): the checks every entry point begins with, the handle's scratch as a bump allocator, the routes of mask inputs and mask
 // outputs, and the arrays of the chain calls -- their checks (with cvs_chain_table.h, the rules of a HOST chain table) and their staging
 // (Staged).  Internal; the overlap rule of the tail is check_disjoint (cvs_context.h).
 #pragma once
@@ -62,8 +62,8 @@ cvs_plane array_plane(const void* p, long long n, int words, int mem);
 // queued: device-only scratch (always in cvs_context::ch_scr), inputs and outputs (the caller's own pointer for a DEVICE call, for which
 // nothing is reserved; a slice of ch_scr for a HOST call; nullptr for an array the caller left out).  Then commit() -- one grow_scratch, which
 // points every bound field into the block --, upload(), the launches, and fetch().  So "stage, launch, fetch" is one order for every call.
-// commit() refuses (CVS_E_UNSUPPORTED) to grow the block while the stream is captured.  Of the calls in front of it only cvs_chain_joins and cvs_chain_paths can
-// meet that: the others reserve nothing for a DEVICE call, and have refused a captured HOST call before they stage.
+// commit() refuses (CVS_E_UNSUPPORTED) to grow the block while the stream is captured.  Of the calls in front of it only cvs_chain_joins, cvs_chain_paths
+// and cvs_chain_bridges can meet that: the others reserve nothing for a DEVICE call, and have refused a captured HOST call before they stage.
 // Whether and where a call sets the device stays its own business (only a call that allocates has to).
 class Staged {
 public:

@@ -379,6 +379,65 @@ int stitch_contours(cvs_handle h, const std::vector<std::vector<Point> >& chains
     return CVS_OK;
 }
 
+// cvs_chain_bridges on host arrays, on the integer points: the chains packed as for the joins, one call with room for every bridge there can
+// be (one per chain, max_gap + 1 points each), and the bridged table unpacked -- the chains, then the bridges, and for stitch_contours the
+// partners the bridges make: the smaller end of a pair continues into the bridge's head, the bridge's tail into the larger end
+int bridge_contours(cvs_handle h, const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags, int radius, int maxGap,
+                    float minCosine, std::vector<std::vector<Point> >& bridged, std::vector<int>& bridgedFlags, std::vector<int>* partners, int* n)
+{
+    if (flags && flags->size() != chains.size()) return CVS_E_BADARG;
+    if (maxGap < 2 || maxGap > CVS_BRIDGE_MAX_GAP) return CVS_E_BADARG;
+    size_t np = 0;
+    for (size_t c = 0; c < chains.size(); ++c) np += chains[c].size();
+    const size_t capPoints = np + chains.size() * ((size_t)maxGap + 1), capChains = 2 * chains.size();
+    if (np > (size_t)1 << 30 || chains.size() > (size_t)1 << 26 || capPoints > (size_t)0x7fffffff) return CVS_E_SIZE;
+    std::vector<int32_t> pts(np * 2), out(capPoints * 2);
+    std::vector<cvs_chain> tab(chains.size()), otab(capChains);
+    std::vector<cvs_chain_bridge> rec(2 * chains.size());
+    size_t at = 0;
+    for (size_t c = 0; c < chains.size(); ++c) {
+        tab[c].start = (int32_t)at;
+        tab[c].length = (int32_t)chains[c].size();
+        tab[c].flags = flags ? (*flags)[c] : 0;
+        tab[c].reserved = 0;
+        for (size_t k = 0; k < chains[c].size(); ++k, ++at) {
+            pts[2 * at] = chains[c][k].x;
+            pts[2 * at + 1] = chains[c][k].y;
+        }
+    }
+    cvs_bridge_cfg cfg;
+    cfg.radius = radius;
+    cfg.min_arm = radius < 3 ? radius : 3;
+    cfg.max_gap = maxGap;
+    cfg.min_cos = minCosine;
+    int32_t counts[3] = {0, 0, 0};
+    const int rc = cvs_chain_bridges(h, pts.data(), (int)np, tab.data(), (int)chains.size(), 0, &cfg, rec.data(), chains.empty() ? 0 : out.data(),
+                                     chains.empty() ? 0 : (int)capPoints, chains.empty() ? 0 : otab.data(), chains.empty() ? 0 : (int)capChains, 0,
+                                     counts, CVS_MEM_HOST);
+    if (rc != CVS_OK) return rc;
+    const size_t total = (size_t)counts[1];
+    if (total > capChains || (size_t)counts[2] > capPoints) return CVS_E_HIP;   // (never: the capacities hold every bridge there can be)
+    bridged.assign(total, std::vector<Point>());
+    bridgedFlags.assign(total, 0);
+    for (size_t c = 0; c < total; ++c) {
+        bridged[c].reserve((size_t)otab[c].length);
+        for (int32_t k = otab[c].start; k < otab[c].start + otab[c].length; ++k) bridged[c].push_back(Point(out[2 * (size_t)k], out[2 * (size_t)k + 1]));
+        bridgedFlags[c] = otab[c].flags;
+    }
+    if (partners) {
+        partners->assign(2 * total, -1);
+        for (size_t e = 0; e < rec.size(); ++e) {
+            const cvs_chain_bridge& b = rec[e];
+            if (!(b.flags & CVS_BRIDGE_MUTUAL) || b.bridge < 0) continue;
+            const int end = 2 * ((int)chains.size() + b.bridge) + ((size_t)b.partner > e ? 0 : 1);   // the smaller end meets the bridge's head
+            (*partners)[e] = end;
+            (*partners)[(size_t)end] = (int)e;
+        }
+    }
+    *n = counts[0];
+    return CVS_OK;
+}
+
 }  // namespace
 
 // --------------------------------------------------------------------------- base
@@ -679,6 +738,14 @@ int SteerableFiltersG2::stitchContours(const std::vector<std::vector<Point> >& c
     return n;
 }
 
+int SteerableFiltersG2::bridgeContours(const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags, int radius, int maxGap, float minCosine,
+                                       std::vector<std::vector<Point> >& bridged, std::vector<int>& bridgedFlags, std::vector<int>* partners)
+{
+    int n = 0;
+    check(bridge_contours(m_handle, chains, flags, radius, maxGap, minCosine, bridged, bridgedFlags, partners, &n), "cvs_chain_bridges");
+    return n;
+}
+
 void SteerableFiltersG2::phaseWeights(const Mat1f& phase, Mat1f& lambda, float phi, bool signum, float k)
 {
     std::lock_guard<std::mutex> lock(g_static_mutex);
@@ -870,6 +937,14 @@ int SteerableFiltersG4::stitchContours(const std::vector<std::vector<Point> >& c
 {
     int n = 0;
     check(stitch_contours(m_handle, chains, flags, partners, paths, pathFlags, members, &n), "cvs_chain_paths");
+    return n;
+}
+
+int SteerableFiltersG4::bridgeContours(const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags, int radius, int maxGap, float minCosine,
+                                       std::vector<std::vector<Point> >& bridged, std::vector<int>& bridgedFlags, std::vector<int>* partners)
+{
+    int n = 0;
+    check(bridge_contours(m_handle, chains, flags, radius, maxGap, minCosine, bridged, bridgedFlags, partners, &n), "cvs_chain_bridges");
     return n;
 }
 

@@ -67,6 +67,15 @@ public:
     // p, in walk order.  Paths are ordered by the contract of include/cvsteer_hip.h.  Returns the number of paths
     int stitchContours(const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags, const std::vector<int>& partners,
                        std::vector<std::vector<Point> >& paths, std::vector<int>* pathFlags = 0, std::vector<std::vector<int> >* members = 0);
+    // contour bridges (extension, cvs_chain_bridges): the gaps between free chain ends that face each other, closed -- chains and flags as
+    // traceContours or stitchContours gave them, on their integer points, by the contract of include/cvsteer_hip.h with min_arm =
+    // min(3, radius): two free ends whose pixels are 2 .. maxGap apart, each pointing at the other within minCosine and each the other's
+    // nearest such end, get a bridge, a digital line from the one end pixel to the other.  bridged = the chains followed by the bridges,
+    // bridgedFlags their flags (a bridged end reads as a junction); partners (optional): 2 entries per bridged chain as joinContours
+    // returns them, naming for every bridged end the bridge end that continues it and the reverse, -1 elsewhere -- so
+    // stitchContours(bridged, &bridgedFlags, partners, paths) puts the dashes of a line together.  Returns the number of bridges
+    int bridgeContours(const std::vector<std::vector<Point> >& chains, const std::vector<int>* flags, int radius, int maxGap, float minCosine,
+                       std::vector<std::vector<Point> >& bridged, std::vector<int>& bridgedFlags, std::vector<int>* partners = 0);
 
 protected:
     // the reference's protected members, same names (SteerableFiltersG4.h:50-56): 11 tap vectors; the planes m_g4a..m_h4f

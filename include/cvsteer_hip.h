@@ -827,6 +827,103 @@ int cvs_chain_paths(cvs_handle h, const int32_t* points, int n_points, const cvs
                     int32_t* counts,                  /* 2 ints, same mem: n_paths, n_path_points */
                     int mem);
 
+/* EXTENSION: contour bridges -- the gaps hysteresis leaves in a contour, closed: two FREE chain ends that face each other across a few
+ * missing pixels are paired off, and each pair is given a BRIDGE, a digital line from the one end pixel to the other.  A bridge is an
+ * ordinary chain appended to the chain table: (points, chains) becomes (out_points, out_chains), and on that pair cvs_chain_joins finds
+ * a node of degree 2 at either end pixel of a bridge and cvs_chain_paths stitches through it, listing the shared pixel once.  One
+ * fixed-size record per chain END says what became of the end.  Needs no image size.
+ * ENDS AND ARMS are those of cvs_chain_joins, to the bit.  Chain c = (S, L, F, R) = chains[c]; its head, end 2c, sits at position j = S
+ * (sign +1), its tail, end 2c+1, at j = S+L-1 (sign -1).  A chain with CVS_CHAIN_CLOSED or L < 2 has no ends: both its records are
+ * partner = bridge = start = -1, n = steps = 0, cos = cos_partner = NaN (every NaN stored is 0x7FC00000), flags = CVS_BRIDGE_NONE.  The
+ * arm: n = min(radius, L-1) points; term k = (x[j +- k] - x[j], y[j +- k] - y[j]), the coordinates of a point being its pair of `xy`
+ * widened to double when xy != NULL, else its integer point; IEEE double, every operation rounded on its own, the terms added in
+ * ascending k starting from term 1; a = sum / (double)n, len = sqrt(a.x*a.x + a.y*a.y), both correctly rounded.  CVS_BRIDGE_SHORT iff
+ * n < min_arm; CVS_BRIDGE_DEGENERATE iff !(len > 0) or len is not finite.
+ * FREE.  An end is FREE iff its junction bit in F is clear -- the head reads CVS_CHAIN_HEAD_JUNCTION, the tail CVS_CHAIN_TAIL_JUNCTION; an
+ * end that exists and is not free gets CVS_BRIDGE_JUNCTION.  Only those two bits and CVS_CHAIN_CLOSED are read of F, so a table of
+ * cvs_contour_chains / _batch and a table of cvs_chain_paths (whose flags carry the junction bits of a path's outer ends) both go
+ * through as they are.  A CANDIDATE is an end with none of NONE, NO_CHAIN, JUNCTION, SHORT, DEGENERATE and CROWDED (below).
+ * CROWDING, the static bound.  The cell of an end is (R, floor(y / max_gap), floor(x / max_gap)) of its INTEGER point (floor division:
+ * coordinates may be negative).  The ends that would be candidates but for CROWDED are counted per cell; a cell that holds more than
+ * CVS_BRIDGE_MAX_CELL = 32 of them is crowded, and every end that exists and has a crowded cell among the 3 x 3 cells around its own
+ * (same R) gets CVS_BRIDGE_CROWDED: it has no partner and is nobody's candidate.  Every end within max_gap of an end lies in those nine
+ * cells, so no end is ever compared with more than 9 x 32 others.
+ * PAIR.  For candidates e != f with the same plane word R, lo = min(e, f), hi = max(e, f); f == e^1 is allowed (a contour that nearly
+ * closes on itself).  On the INTEGER points, in 64-bit integers: dx = x_hi - x_lo, dy = y_hi - y_lo, steps = max(|dx|, |dy|), d2 =
+ * dx*dx + dy*dy.  The pair is IN RANGE iff 2 <= steps <= max_gap.  In doubles, with D = coords(hi) - coords(lo) (coords as for the
+ * arm) and dlen = sqrt(D.x*D.x + D.y*D.y): cos_lo = (float)(-(a_lo.x*D.x + a_lo.y*D.y) / (len_lo*dlen)), cos_hi = (float)((a_hi.x*D.x +
+ * a_hi.y*D.y) / (len_hi*dlen)) -- 1 where the end points straight at the other.  The pair is always evaluated from lo, so both ends see
+ * the same bits.  It is ADMISSIBLE iff it is in range, dlen is finite and > 0, and cos_lo >= min_cos and cos_hi >= min_cos (float
+ * comparisons: false for NaN).
+ * PARTNER.  partner(e) = the f of the admissible pairs (e, f) with the smallest (d2, f), lexicographically; steps, cos (this end's
+ * cosine) and cos_partner (the partner's) are those of that pair.  None: partner = -1, steps = 0, NaN.  CVS_BRIDGE_MUTUAL iff
+ * partner(partner(e)) == e: admissibility and d2 are symmetric, so MUTUAL pairs ends off.
+ * BRIDGES.  The MUTUAL pairs are numbered by ascending lo.  Bridge k has steps+1 points and is chain n_chains + k; its first point is
+ * out_points[n_points + (sum of steps+1 over the bridges before it)].  Point j = 0 .. steps is (x_lo + floor((2*j*dx + steps) /
+ * (2*steps)), y_lo + floor((2*j*dy + steps) / (2*steps))) in 64-bit integers: an 8-connected line whose point 0 is lo's pixel and whose
+ * point `steps` is hi's.  Its entry is (start, steps+1, CVS_CHAIN_HEAD_JUNCTION | CVS_CHAIN_TAIL_JUNCTION, R).  With xy, out_xy of its
+ * points 0 and steps are the bits of the two ends' xy and of point j between them (float)(c_lo + t*(c_hi - c_lo)), t = (double)j /
+ * (double)steps, per coordinate, every operation rounded in double.  out_points[0 .. n_points), out_xy[0 .. n_points) and out_chains[0 ..
+ * n_chains) are copies of the inputs, with the junction bit of every MUTUAL end set in the copy of its chain's flags (so the next
+ * cvs_chain_bridges leaves it alone and a path through it reads as continued).  table[e].bridge and .start are k and the index of the
+ * bridge's first point, on both ends of the pair; -1 on every other end.
+ * CAPACITIES.  counts = (n_bridges, n_chains + n_bridges, n_points + all bridge points): the full totals, always.  Bridge k is WRITTEN
+ * iff n_chains + k < cap_chains and the index of its last point is < cap_points -- a prefix of the bridges; no entry and no point of
+ * another bridge is touched, and nothing past the capacities ever.  The table does not depend on the capacities.  With out_points ==
+ * NULL (then out_chains and out_xy are NULL and both capacities 0) only the table and the counts are written: the sizing call.
+ * n_points + bridge points stays below 2^32; where it passes 2^31 - 1, counts[2] and start hold its low 32 bits (no such bridge is ever
+ * written: cap_points is an int).
+ * MEMORY.  All arrays are in host or all in device memory (mem).  HOST: `chains` is checked in full -- CVS_E_BADARG unless the starts are
+ * the running sum of the lengths from 0 to n_points and every length is >= 1; the arrays are staged in handle scratch, the call
+ * synchronises, copies out the table, the counts and what was written of the outputs, and returns CVS_E_UNSUPPORTED while the stream is
+ * being captured.  DEVICE: tables are trusted for nothing -- an entry that fails S >= 0, L >= 1, S + L <= n_points gets the records of a
+ * chain without ends with CVS_BRIDGE_NO_CHAIN added (its copy in out_chains is still the entry as it is); entries may overlap or leave
+ * gaps; every index is checked before it is an address and coordinates are never addresses, so no load and no store leaves the arrays.
+ * EXECUTION.  One lane per end: the arms and cells, the grouping of the candidates by cell in a hash table, the crowding, the choice
+ * of the partner, MUTUAL; a scan over the ends that numbers the bridges and sums their points; the records and entries; then one lane
+ * per output point, each bridge point computed on its own.  8 launches, 9 with outputs, whatever the arrays hold -- arrays of
+ * arbitrary bytes take the same launches as good ones; no kernel has a loop without a static bound, none waits or spins, the atomics
+ * are integer.  Queued on the handle's stream, nothing read back, nothing synchronised, capturable.  The result is a function of the
+ * inputs alone: the same call twice gives the same bytes (which slot a cell gets and the order of its list depend on a race; no output
+ * does).  Handle scratch (grown only, freed by cvs_destroy): CVS_BRIDGE_SCRATCH_PER_CHAIN = 244 bytes per chain (120 per end, 4 per
+ * possible bridge), 16 bytes per slot of a table of max(8, the power of two >= 4 n_chains) slots, 8 bytes per 1024 ends and less than
+ * 2 KiB of rounding.  A call that would have to GROW the scratch while the stream is being captured returns CVS_E_UNSUPPORTED ("call
+ * once eagerly first", the rule of cvs_chain_joins); the handle works on.  n_chains == 0: counts = (0, 0, 0), CVS_OK.
+ * CVS_E_BADARG, nothing written: cfg NULL, radius outside 1 .. 64, min_arm outside 1 .. radius, max_gap outside 2 .. 32, min_cos NaN or
+ * outside -1 .. 1; a negative count; a required array missing (counts; points with n_points > 0; chains / table with n_chains > 0);
+ * out_points without out_chains or the reverse; a capacity != 0 without its array; cap_points < n_points or cap_chains < n_chains;
+ * out_xy without xy or without out_points, or xy and out_points without out_xy; n_points > 0 with n_chains == 0; an invalid mem; a
+ * pointer not aligned to 4 bytes; an output overlapping an input or another output; a HOST table as above.  n_points > 2^30 or n_chains
+ * > 2^26: CVS_E_SIZE.
+ * Out of scope: bridging a free end to the SIDE of a contour, testing the line against the mask, a strength for bridge points. */
+typedef struct cvs_bridge_cfg {
+    int32_t radius;    /* 1..64: points per arm, the arm of cvs_chain_joins */
+    int32_t min_arm;   /* 1..radius: an end with a shorter arm bridges nothing */
+    int32_t max_gap;   /* 2..32: largest Chebyshev distance between the two end pixels */
+    float   min_cos;   /* -1..1, NaN refused: each end must point at the other within this cone */
+} cvs_bridge_cfg;
+typedef struct cvs_chain_bridge {    /* 32 bytes, one per chain END: record 2c = head of chain c, 2c+1 = tail */
+    int32_t partner;                 /* the free end this one would bridge to; -1 */
+    int32_t flags;                   /* CVS_BRIDGE_MUTUAL = 1, _NONE = 2, _JUNCTION = 4, _SHORT = 8, _DEGENERATE = 16, _NO_CHAIN = 32, _CROWDED = 64 */
+    int32_t n;                       /* points of the arm */
+    int32_t steps;                   /* Chebyshev distance to partner; 0 without */
+    int32_t bridge;                  /* number of the bridge, on both ends of a MUTUAL pair; -1 */
+    int32_t start;                   /* index in out_points of the bridge's first point; -1 */
+    float   cos, cos_partner;        /* this end's and the partner's pointing cosine; NaN without partner */
+} cvs_chain_bridge;
+enum { CVS_BRIDGE_MUTUAL = 1, CVS_BRIDGE_NONE = 2, CVS_BRIDGE_JUNCTION = 4, CVS_BRIDGE_SHORT = 8, CVS_BRIDGE_DEGENERATE = 16,
+       CVS_BRIDGE_NO_CHAIN = 32, CVS_BRIDGE_CROWDED = 64 };
+enum { CVS_BRIDGE_SCRATCH_PER_CHAIN = 244, CVS_BRIDGE_MAX_GAP = 32, CVS_BRIDGE_MAX_CELL = 32 };
+int cvs_chain_bridges(cvs_handle h, const int32_t* points, int n_points, const cvs_chain* chains, int n_chains,
+                      const float* xy,                         /* NULL: the integer points */
+                      const cvs_bridge_cfg* cfg,
+                      cvs_chain_bridge* table,                 /* 2 * n_chains records */
+                      int32_t* out_points, int cap_points,     /* NULL/0, or room for cap_points >= n_points pairs */
+                      cvs_chain* out_chains, int cap_chains,   /* NULL/0, or room for cap_chains >= n_chains entries */
+                      float* out_xy,                           /* required iff xy != NULL and out_points != NULL */
+                      int32_t* counts,                         /* 3 ints, same mem: n_bridges, n_out_chains, n_out_points */
+                      int mem);
+
 /* ---- EXTENSION beyond the reference: the contour chain on the batch axis -- cvs_link, cvs_nonmax_batch, cvs_contours_batch ----
  * None of the three reads anything back: with device planes they queue a launch sequence that depends on the image size, the number of
  * planes and how the planes lie in memory (one constant stride, or not) -- never on what the planes hold -- and return. */
